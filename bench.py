@@ -9,9 +9,13 @@ step     one pass of the hot path: out = M @ X + b (GCNConv propagate + bias, la
 N > 1    the SAME graph 1-D row-partitioned over N GPUs ("strong" scaling): per SpMM one RCCL
          all-gather of the row-sharded operand, then the local row block (pytextgcn_amd/sharded.py).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel:
-the CSR gather SpMM, HBM-bound) and `cpu_baseline` (the oracle's reference formulation timed on
-this box's host cores over a bounded sample of the same workload).
+Prints ONE JSON line on rank 0: the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step`, ...).  A plain run does nothing else: set up, W warm-up steps, K timed steps, the
+outputs of the last one when --dump-outputs DIR is given, the line.  --full adds everything else
+to the same line: `roofline` (dominant kernel: the CSR gather SpMM, HBM-bound), the accurate mode
+beside the headline, the epoch figures, at N > 1 the parity check and exchange diagnostics, and
+`cpu_baseline` (the oracle's reference formulation timed on this box's host cores over a bounded
+sample of the same workload).
 """
 from __future__ import annotations
 
@@ -37,6 +41,8 @@ CONFIGS = {
 }
 HBM_PEAK_GBPS = 8000.0      # MI355X HBM3E spec peak (MI355X_MICROARCH.md, chip-level parameters)
 FABRIC_GATHER_CEILING_GBPS = 8600.0   # MI355X_MICROARCH.md 'Indexed rows': random rows of an Infinity-Cache-resident table
+DUMP_BYTES = 64_000_000    # --dump-outputs: what all ranks together write at most (.npy headers included)
+DUMP_SEED = 2024            # --dump-outputs: seed of the row sample
 
 
 def parse():
@@ -62,10 +68,22 @@ def parse():
     p.add_argument("--mode", choices=["both", "reference", "accurate"], default="both",
                    help="normalisation mode of the operator (pytextgcn_amd.plan): the headline `value` is ALWAYS the "
                         "reference-order mode's unless --mode accurate; `both` (default) additionally times the accurate "
-                        "mode in the same run at N = 1 (`value_accurate_mode`)")
+                        "mode in the same run at N = 1 with --full (`value_accurate_mode`)")
     p.add_argument("--launch-check", action="store_true",
                    help="rendezvous only: every rank joins the group, rank 0 prints {launch_check, n_gpus}; no GPU work")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline: the accurate mode beside it, the roofline and its traffic "
+                        "measurements, the epoch figures, the N > 1 parity check and diagnostics, the CPU baselines; a plain "
+                        "run sets up, warms up, times the steps and prints the headline only")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last of them computed (both SpMM products, the rows of a "
+                        f"fixed seeded sample, at most {DUMP_BYTES // 10**6} MB in all) as DIR/<name>.npy in float32, the "
+                        "sampled row indices as DIR/sample_rows.npy in float64; N > 1: per rank, *_rank<r>.npy, indices local to "
+                        "the rank's rows")
+    args = p.parse_args()
+    if args.epoch_matrix and not args.full:
+        p.error("--epoch-matrix is part of the full record: add --full")
+    return args
 
 
 def _run_ranks(cmd, env, budget_s):
@@ -940,6 +958,32 @@ def exchange_diagnostics(sg, F, dev, dist, reps=10):
     return out
 
 
+def dump_outputs(directory, arrays, rank, world):
+    """--dump-outputs: `arrays` ({name: [rows, F] device tensor}, what the last timed step handed its caller) as
+    DIR/<name>.npy in float32, restricted to a fixed sample of rows drawn with DUMP_SEED (sorted; all rows when they fit),
+    and the sampled row indices as DIR/sample_rows.npy (float64, exact).  N > 1: each rank writes the rows it owns, under
+    names ending in _rank<r>, and the ranks share the DUMP_BYTES cap; its sample_rows then index the rank's LOCAL rows (the
+    order of ShardedGraph's partition, not global node ids), so dumps line up between runs at the same world size only.
+    Returns the paths written."""
+    import numpy as np
+    n_rows = next(iter(arrays.values())).shape[0]
+    row_bytes = 8 + sum(4 * a[0].numel() for a in arrays.values())
+    n_keep = min(n_rows, (DUMP_BYTES // world - 1024 * (len(arrays) + 1)) // row_bytes)      # (1 KiB per header)
+    rows = torch.arange(n_rows)
+    if n_keep < n_rows:
+        gen = torch.Generator().manual_seed(DUMP_SEED + rank)
+        rows = torch.randperm(n_rows, generator=gen)[:n_keep].sort().values
+    suffix = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(directory, exist_ok=True)
+    written = []
+    for name, a in dict(arrays, sample_rows=None).items():
+        host = rows.double() if a is None else a.index_select(0, rows.to(a.device)).float().cpu()
+        path = os.path.join(directory, name + suffix + ".npy")
+        np.save(path, host.numpy())
+        written.append(path)
+    return written
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -1070,16 +1114,19 @@ def main():
         sg = ShardedGraph(g.edge_index, g.edge_attr, N, group=dist.group.WORLD, hubs=hubs, degree_sum=headline_mode)
         x = torch.randn(sg.n_local, F, device=dev, generator=gen)
         gout = torch.randn(sg.n_local, F, device=dev, generator=gen)
+        last = {} if args.dump_outputs is not None else None     # --dump-outputs: the products of the latest step
 
         def step(ev=None):
             if ev is not None:
                 ev[0].record()
-            sg.spmm(x, bias)
+            y_ = sg.spmm(x, bias)
             if ev is not None:
                 ev[1].record()
-            sg.spmm(gout, None, transpose=True)
+            dxw_ = sg.spmm(gout, None, transpose=True)
             if ev is not None:
                 ev[2].record()
+            if last is not None:
+                last.update(spmm_forward=y_, spmm_transposed=dxw_)
         plan = sg.plan
         ops_f = [op for op in sg.ops[0] if op is not None]
         ops_b = [op for op in sg.ops[-1] if op is not None]
@@ -1208,23 +1255,12 @@ def main():
     note("operators built; timing the headline", rank)
     elapsed, ms_fwd, ms_bwd = timed(step)
     note(f"headline timed: {elapsed / args.steps * 1e3:.3f} ms per step", rank)
-    launch_ms = 0.5 * (ms_fwd + ms_bwd)
-    # the accurate mode beside it: same graph, same operands, same K / W, same bracket (N = 1)
-    other_mode = None
-    if parallelism == "single" and args.mode == "both":
-        plan_acc = GraphPlan(g.edge_index, g.edge_attr, N, degree_sum="accurate")
-        el2, f2, b2 = timed(make_step(plan_acc))
-        other_mode = {"mode": "accurate", "value": 2.0 * E / (el2 / args.steps), "ms_per_step": el2 / args.steps * 1e3,
-                      "launch_ms_fwd": f2, "launch_ms_bwd": b2, "stores_transpose": not plan_acc.symmetric,
-                      "plan_device_bytes": plan_acc.stats()["device_bytes"]}
-        plan_acc.close()
-        del plan_acc
-    launch_bytes = 0.5 * (bytes_fwd + bytes_bwd)
-    achieved = launch_bytes / (launch_ms * 1e-3) / 1e9
-
-    # ---- the headline, complete at this point; everything below is secondary ------------------------------------------
-    secondary_errors = {}
-    completed = {}                     # results of the secondary measurements that finished: an aborted record keeps them
+    if args.dump_outputs is not None:
+        # before anything else runs: the accurate mode of --full writes into the same output buffers
+        written = dump_outputs(args.dump_outputs, {"spmm_forward": y, "spmm_transposed": dxw} if parallelism == "single"
+                               else dict(last), rank, world)
+        last = None                      # (the later steps of --full keep no references)
+        note(f"outputs of the last timed step written: {', '.join(written)}", rank)
     workload = (f"{args.config}: synthetic {'power-law graph' if args.config in ('c5', 'c5s') else 'PMI/TF-IDF word-doc graph'}, N={N}, "
                 f"E={E}, nnz={E + N} (with self loops), F={F}, seed 44; step = M@X+b and M^T@G; "
                 + ("normalisation mode 'reference' (PyG-1.6.3 gcn_norm's own fp32 arithmetic, weights bit for bit the "
@@ -1243,6 +1279,31 @@ def main():
         if rank == 0 and not state["written"]:
             state["written"] = True
             os.write(json_fd, (json.dumps(rec) + "\n").encode())
+    if not args.full:
+        # a plain run: the headline is all it measures (everything below is --full)
+        write_record(dict(headline, exchange_selection=exchange_selection, setup_s=setup_s))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    launch_ms = 0.5 * (ms_fwd + ms_bwd)
+    # the accurate mode beside it: same graph, same operands, same K / W, same bracket (N = 1)
+    other_mode = None
+    if parallelism == "single" and args.mode == "both":
+        plan_acc = GraphPlan(g.edge_index, g.edge_attr, N, degree_sum="accurate")
+        el2, f2, b2 = timed(make_step(plan_acc))
+        other_mode = {"mode": "accurate", "value": 2.0 * E / (el2 / args.steps), "ms_per_step": el2 / args.steps * 1e3,
+                      "launch_ms_fwd": f2, "launch_ms_bwd": b2, "stores_transpose": not plan_acc.symmetric,
+                      "plan_device_bytes": plan_acc.stats()["device_bytes"]}
+        plan_acc.close()
+        del plan_acc
+    launch_bytes = 0.5 * (bytes_fwd + bytes_bwd)
+    achieved = launch_bytes / (launch_ms * 1e-3) / 1e9
+
+    # ---- the headline, complete at this point; everything below is secondary ------------------------------------------
+    secondary_errors = {}
+    completed = {}                     # results of the secondary measurements that finished: an aborted record keeps them
 
     def abort(where, err):
         """A failure that must not be swallowed (see `secondary`): rank 0 writes the headline it holds, marked as an aborted

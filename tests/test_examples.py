@@ -93,10 +93,10 @@ def test_multi_gpu_script_under_gloo_world_2(cuda, extra):
 
 
 def test_bench_single_gpu_record_and_its_epoch_matrix(cuda):
-    """`python bench.py --config c2 --epoch-matrix` on the test box's GPU (no rocprofv3 child runs, no CPU leg): the contract
+    """`python bench.py --full --config c2 --epoch-matrix` on the test box's GPU (no rocprofv3 child runs, no CPU leg): the contract
     keys, the roofline object, the FOUR epoch figures a record carries and -- with the flag -- the switches one by one."""
     import json
-    out = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c2", "--steps", "5", "--warmup", "2",
+    out = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", "c2", "--steps", "5", "--warmup", "2",
                 "--no-cpu-baseline", "--no-live-traffic", "--no-hbm-activity", "--epoch-matrix"], timeout=600)
     lines = [ln for ln in out.splitlines() if ln.strip().startswith("{")]
     assert len(lines) == 1, out[-1500:]
@@ -116,3 +116,43 @@ def test_bench_single_gpu_record_and_its_epoch_matrix(cuda):
                       "fused_w1_reuse_needed_rows_only", "fused_w1_reuse_split_bf16_gemms"}
     assert all(isinstance(v, float) and v > 0 for v in m.values()), m
     assert d["secondary_errors"] is None
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_the_products_of_its_last_step(cuda, tmp_path):
+    """`python bench.py --config c2 --steps 4 --warmup 1 --dump-outputs DIR`: one line holding the headline and nothing of
+    the full record, and in DIR the rows of a seeded sample of both SpMM products of the last timed step -- the products of
+    the same inputs recomputed in float64 on the host from the oracle's normalised operator, at 1e-5."""
+    import json
+    import numpy as np
+    import torch
+    from oracle import gcn_oracle as O
+    from pytextgcn_amd import synth
+    out = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c2", "--steps", "4", "--warmup", "1",
+                "--dump-outputs", str(tmp_path)], timeout=600)
+    lines = [ln for ln in out.splitlines() if ln.strip().startswith("{")]
+    assert len(lines) == 1, out[-1500:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert k in d, k
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["unit"] == "edges/s" and d["dtype"] == "f32"
+    assert abs(d["value"] - 2 * 2_000_000 / (d["ms_per_step"] * 1e-3)) < 1e-3 * d["value"]
+    assert not {"roofline", "accurate_mode", "epoch_ms", "cpu_baseline", "rccl"} & set(d), sorted(d)
+    names = ("spmm_forward", "spmm_transposed", "sample_rows")
+    assert sorted(p.name for p in tmp_path.iterdir()) == sorted(n + ".npy" for n in names)
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) <= 64_000_000
+    fwd, bwd, rows = (np.load(tmp_path / (n + ".npy")) for n in names)
+    assert fwd.dtype == bwd.dtype == np.float32 and rows.dtype == np.float64
+    rows = torch.from_numpy(rows.astype(np.int64))
+    # bench.py's inputs: graph c2 (seed 44; synth draws on the host), then bias, X and G from one device generator
+    N, E, F, C = 100_000, 2_000_000, 200, 64
+    g = synth.word_doc_graph(N, E, seed=44, n_classes=C, features="none")
+    gen = torch.Generator(device=cuda).manual_seed(1234)
+    bias, x, gout = (torch.randn(*shape, device=cuda, generator=gen).double().cpu() for shape in ((F,), (N, F), (N, F)))
+    tgt, src, nw = O.normalized_coo(g.edge_index, g.edge_attr, N)
+    M = torch.sparse_coo_tensor(torch.stack([tgt, src]), nw.double(), (N, N)).coalesce()
+    want_fwd = (torch.sparse.mm(M, x) + bias)[rows]
+    want_bwd = torch.sparse.mm(M.t().coalesce(), gout)[rows]
+    for got, want in ((fwd, want_fwd), (bwd, want_bwd)):
+        assert got.shape == tuple(want.shape)
+        err = (torch.from_numpy(got).double() - want).abs().max().item() / want.abs().max().item()
+        assert err < 1e-5, err

@@ -3,6 +3,7 @@ against the reference's own golden (textgcn/test/test_cfunc.py:83-99) and agains
 by the reference module itself (tests/golden/graphbuilder_ref.npz).  GPU part: the HIP builder,
 through the C ABI, bit-exact against the oracle and the same vectors."""
 import os
+import warnings
 
 import numpy as np
 import pytest
@@ -43,15 +44,22 @@ def test_oracle_equals_vectors_from_the_reference_module():
 
 
 def test_oracle_against_live_reference_module_when_built():
+    """The reference module on the golden input of test_cfunc.py against the oracle: its outputs as recorded in
+    tests/golden/graphbuilder_ref.npz (case 0), and the live module as well where oracle/_ref was built -- where it was
+    not, the test says so in a warning (the recorded outputs are then the only reference side)."""
+    assert np.array_equal(GOLD["X0"], REF_X) and int(GOLD["V0"]) == 6 and int(GOLD["win0"]) == 3
+    runs = [(GOLD["cij0"], GOLD["coo0"], GOLD["w0"])]
     ref = G.load_ref()
     if ref is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
-    c = np.asarray(ref.sliding_window_tester(REF_X, 6, 2, 8, 3))
-    np.testing.assert_equal(c, REF_CIJ)
-    coo, w = ref.compute_word_word_edges(REF_X, 6, 2, 8, 3)
+        warnings.warn("oracle/_ref is not built: the reference module's recorded outputs were checked, the live module "
+                      "was not")
+    else:
+        runs.append((ref.sliding_window_tester(REF_X, 6, 2, 8, 3),) + tuple(ref.compute_word_word_edges(REF_X, 6, 2, 8, 3)))
     a, b = G.compute_word_word_edges(REF_X, 6, 3)
-    np.testing.assert_equal(np.asarray(coo), a)
-    np.testing.assert_equal(np.asarray(w), b)
+    for c, coo, w in runs:
+        np.testing.assert_equal(np.asarray(c), REF_CIJ)
+        np.testing.assert_equal(np.asarray(coo), a)
+        np.testing.assert_equal(np.asarray(w), b)
 
 
 # both counters of the HIP builder: the dense packed triangle (small vocabularies) and the sorted list of distinct pairs

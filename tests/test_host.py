@@ -279,6 +279,61 @@ def test_bench_falls_back_to_the_plain_configuration_when_the_first_attempt_dies
     assert res.returncode != 0 and not res.stdout.decode().strip()
 
 
+def _bench_module():
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_plain_run_is_the_headline_and_the_rest_is_opt_in(monkeypatch):
+    """A plain command line measures the headline only; `--full` (off by default) opts into everything else, and
+    `--epoch-matrix` -- a part of the full record -- is refused without it instead of being ignored."""
+    bench = _bench_module()
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--epoch-matrix", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.epoch_matrix and a.dump_outputs == "out"
+    monkeypatch.setattr("sys.argv", ["bench.py", "--epoch-matrix"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+@pytest.mark.parametrize("world", [1, 3])
+def test_bench_dump_outputs_writes_a_fixed_sample_within_the_cap(tmp_path, world):
+    """`--dump-outputs`: float32 rows of every product at the same sampled rows (sorted, float64 indices), the same sample
+    on every call, every rank's share within DUMP_BYTES / world; all rows when they fit."""
+    import os
+    import numpy as np
+    bench = _bench_module()
+    n, F = 60_000, 200
+    fwd = torch.arange(n * F, dtype=torch.float32).reshape(n, F)
+    arrays = {"spmm_forward": fwd, "spmm_transposed": -fwd}
+    rank = world - 1
+    sfx = f"_rank{rank}" if world > 1 else ""
+    paths = bench.dump_outputs(str(tmp_path / "a"), arrays, rank, world)
+    assert sorted(os.path.basename(p) for p in paths) == sorted(f"{k}{sfx}.npy" for k in
+                                                                 ("spmm_forward", "spmm_transposed", "sample_rows"))
+    rows = np.load(tmp_path / "a" / f"sample_rows{sfx}.npy")
+    f = np.load(tmp_path / "a" / f"spmm_forward{sfx}.npy")
+    t = np.load(tmp_path / "a" / f"spmm_transposed{sfx}.npy")
+    assert rows.dtype == np.float64 and f.dtype == np.float32 and t.dtype == np.float32
+    assert sum(os.path.getsize(p) for p in paths) <= bench.DUMP_BYTES // world
+    assert 0 < len(rows) < n and np.all(np.diff(rows) > 0) and f.shape == t.shape == (len(rows), F)
+    np.testing.assert_array_equal(f, fwd.numpy()[rows.astype(np.int64)])
+    np.testing.assert_array_equal(t, -f)
+    bench.dump_outputs(str(tmp_path / "b"), arrays, rank, world)
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / f"sample_rows{sfx}.npy"), rows)
+    small = {"spmm_forward": fwd[:100]}
+    bench.dump_outputs(str(tmp_path / "c"), small, rank, world)
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / f"sample_rows{sfx}.npy"), np.arange(100))
+
+
 def test_bench_knows_every_baseline_configuration():
     import importlib.util
     import os

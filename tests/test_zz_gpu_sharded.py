@@ -156,7 +156,7 @@ def test_rccl_ranks_sharing_one_gpu_pipelined_exchange(cuda, monkeypatch, world,
 
 
 def test_bench_two_ranks_as_a_plain_command(cuda):
-    """`python3 bench.py --gpus 2 --config c2` with no launcher around it: two gloo ranks sharing cuda:0 rehearse the
+    """`python3 bench.py --full --gpus 2 --config c2` with no launcher around it: two gloo ranks sharing cuda:0 rehearse the
     whole N > 1 bench (self-launch, graph broadcast, partition, exchange-form trial steps, timed region, sharded epoch)
     and rank 0's single JSON line comes back through the parent."""
     import json
@@ -164,7 +164,7 @@ def test_bench_two_ranks_as_a_plain_command(cuda):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(TGCN_BENCH_BACKEND="gloo", TGCN_BENCH_DEVICE="0")
-    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--config", "c2",
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--config", "c2",
                           "--steps", "3", "--warmup", "1"], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                          env=env, timeout=900)
     assert res.returncode == 0, res.stderr.decode()[-3000:]
@@ -184,7 +184,7 @@ def _bench_two_rccl_ranks(cmd_prefix, extra_env=None):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(TGCN_BENCH_DEVICE="0", **(extra_env or {}))        # backend: the default, "nccl" = RCCL
-    res = subprocess.run(cmd_prefix + [os.path.join(root, "bench.py"), "--gpus", "2", "--config", "c2", "--steps", "3",
+    res = subprocess.run(cmd_prefix + [os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--config", "c2", "--steps", "3",
                                        "--warmup", "1"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env,
                          timeout=900, cwd=root)
     assert res.returncode == 0, res.stderr.decode()[-3000:]
@@ -230,7 +230,7 @@ def test_bench_two_rccl_ranks_without_hub_structure_try_the_pipelined_exchange(c
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(TGCN_BENCH_DEVICE="0")
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-                          "127.0.0.1", "--master-port", str(free_port()), os.path.join(root, "bench.py"), "--gpus", "2",
+                          "127.0.0.1", "--master-port", str(free_port()), os.path.join(root, "bench.py"), "--full", "--gpus", "2",
                           "--config", "c5s", "--steps", "3", "--warmup", "1", "--no-epoch"],
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=900, cwd=root)
     assert res.returncode == 0, res.stderr.decode()[-3000:]
@@ -257,7 +257,7 @@ def test_bench_rank_failing_alone_in_a_secondary_measurement_costs_neither_a_han
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(TGCN_BENCH_BACKEND="gloo", TGCN_BENCH_DEVICE="0", TGCN_BENCH_TEST_FAIL="secondary")
-    args = [os.path.join(root, "bench.py"), "--gpus", "2", "--config", "c2", "--steps", "3", "--warmup", "1"]
+    args = [os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--config", "c2", "--steps", "3", "--warmup", "1"]
     # (1) under the driver's own launch line: a non-zero exit, quickly, and ONE line that still carries the headline
     t0 = time.time()
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",

@@ -9,8 +9,8 @@ QUICK=${2:-}
 mkdir -p $R
 root="$PWD"
 export TMPDIR=/tmp
-BENCH="$root/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-epoch --no-hbm-activity --mode reference"
-echo "python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-epoch --no-hbm-activity --mode reference" > $R/command.txt
+BENCH="$root/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-epoch --no-hbm-activity --mode reference"
+echo "python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-epoch --no-hbm-activity --mode reference" > $R/command.txt
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $root/$R/stats -- python3 $BENCH > $root/$R/stats.log 2>&1 || { tail -5 $root/$R/stats.log; exit 1; }
 echo "stats done"
@@ -21,7 +21,7 @@ if [ -z "$QUICK" ]; then
 rocprofv3 --kernel-trace --stats --output-format csv -d $root/$R/epoch -- python3 $root/tools/profile_epoch.py best > $root/$R/epoch.log 2>&1 || exit 1
 echo "epoch done"
 # config c3 (219 classes): the kernel list of its fused epoch must hold no rocBLAS (Cijk_*) kernel
-rocprofv3 --kernel-trace --stats --output-format csv -d $root/$R/c3 -- python3 $root/bench.py --config c3 --steps 5 --warmup 2 --no-cpu-baseline --no-hbm-activity > $root/$R/c3.log 2>&1 || { tail -5 $root/$R/c3.log; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $root/$R/c3 -- python3 $root/bench.py --full --config c3 --steps 5 --warmup 2 --no-cpu-baseline --no-hbm-activity > $root/$R/c3.log 2>&1 || { tail -5 $root/$R/c3.log; exit 1; }
 echo "c3 done"
 cd $root
 timeout -k 10 600 tools/prof_pmc.sh "$root/$R/pmc_f64" "$root/tools/sweep_spmm.py" one c4 64 > /dev/null || exit 1
@@ -35,7 +35,7 @@ timeout -k 10 300 python tools/hbm_activity.py --out $R/hbm_activity.json > $R/h
 tail -3 $R/hbm_activity.log | cut -c1-200
 fi
 cd $root
-timeout -k 10 600 python bench.py > $R/bench_c4_n1.json 2> $R/bench.err || exit 1
+timeout -k 10 600 python bench.py --full > $R/bench_c4_n1.json 2> $R/bench.err || exit 1
 cut -c1-300 $R/bench_c4_n1.json
 find $R -name "*_agent_info.csv" -delete
 du -sh $R

@@ -13,7 +13,7 @@ for n in "$@"; do
   port=$((port+1))
   echo "== $cfg, $n RCCL ranks on one GPU, torch.distributed.run"
   timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 \
-      --master-port $port bench.py --gpus $n --config $cfg --steps 5 --warmup 1 \
+      --master-port $port bench.py --full --gpus $n --config $cfg --steps 5 --warmup 1 \
       > $R/bench_${cfg}_rccl${n}.json 2> $R/bench_${cfg}_rccl${n}.err || { tail -20 $R/bench_${cfg}_rccl${n}.err; exit 1; }
   python - <<PY
 import json

@@ -12,7 +12,7 @@ mkdir -p $R
 export TMPDIR=/tmp WORLD_SIZE=2 MASTER_ADDR=127.0.0.1 MASTER_PORT=$((29590+K)) TGCN_BENCH_DEVICE=0
 export TGCN_EXCHANGE=$EXCHANGE TGCN_RS_CHUNKS=$K
 if [ -n "${STAGES:-}" ]; then export TGCN_PIPE_STAGES=$STAGES; fi
-ARGS="--gpus 2 --config $CFG --steps 4 --warmup 1 --no-epoch --no-cpu-baseline --no-hbm-activity"
+ARGS="--full --gpus 2 --config $CFG --steps 4 --warmup 1 --no-epoch --no-cpu-baseline --no-hbm-activity"
 RANK=1 LOCAL_RANK=1 timeout -k 10 400 python3 bench.py $ARGS > $R/rank1.out 2> $R/rank1.err &
 peer=$!
 export RANK=0 LOCAL_RANK=0
