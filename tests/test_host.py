@@ -170,32 +170,12 @@ def test_committed_round2_bench_line_carries_a_believable_roofline():
 
 def test_fused_dropout_hash_has_no_measurable_structure():
     """The keep decision of the fused dropout is a stateless hash of (seed, row, col) (csrc/dense.hip: drop_row_key,
-    drop_col_term, drop_elem), restated here in numpy: keep rate, per-column rates and the correlation between
+    drop_col_term, drop_elem), restated in numpy (tests/_dropout_hash.py): keep rate, per-column rates and the correlation between
     adjacent columns, columns two apart and adjacent rows stay within 4 sigma over 4 M elements, for three seeds and
     three rates.  (A one-multiply finaliser fails this at columns two apart, z = +5 ... +6: HISTORY.md 4.5.)  The
     GPU side reads the real mask back in test_fused_dropout_gemms_share_one_mask."""
     import numpy as np
-    m32 = np.uint64(0xFFFFFFFF)
-
-    def u32(x):
-        return x & m32
-
-    def row_key(s_lo, s_hi, row):
-        h = u32(row ^ np.uint64(s_lo))
-        h = u32(h * np.uint64(0xCC9E2D51))
-        h = u32((h << np.uint64(15)) | (h >> np.uint64(17)))
-        h = u32(h * np.uint64(0x1B873593))
-        h = h ^ u32((row >> np.uint64(32)) + np.uint64(s_hi))
-        h = h ^ (h >> np.uint64(16))
-        return u32(h * np.uint64(0x85EBCA6B))
-
-    def elem(key, col):
-        h = u32(key + u32(col * np.uint64(0x9E3779B1)))
-        h = h ^ (h >> np.uint64(15))
-        h = u32(h * np.uint64(0x2C1B3C6D))
-        h = h ^ (h >> np.uint64(12))
-        h = u32(h * np.uint64(0x297A2D39))
-        return h ^ (h >> np.uint64(15))
+    from _dropout_hash import elem, row_key
 
     rows = np.arange(20000, dtype=np.uint64)[:, None]
     cols = np.arange(200, dtype=np.uint64)[None, :]
