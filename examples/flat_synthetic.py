@@ -28,6 +28,7 @@ p.add_argument("--docs", type=int, default=5000)
 p.add_argument("--epochs", type=int, default=50)
 p.add_argument("--fused", action="store_true", help="pytextgcn_amd.train.FlatLoop: the same epoch with every switch of the package instead of torch's CE / Adam / dropout")
 p.add_argument("--preset", choices=["amazon", "dbpedia"], default="amazon", help="hyper-parameters of flat_amazon.py or of flat_dbpedia.py")
+p.add_argument("--relu", action="store_true", help="GCN(apply_activation=True): the ReLU between the layers that the reference comments out (textgcn/lib/models.py:22), fused into the SpMM epilogue")
 p.add_argument("--reorder", action="store_true",
                help="pytextgcn_amd.reorder_documents: lay the document nodes out by clusters found from the graph (a corpus "
                     "with topical locality whose file is not sorted by class gathers fewer distinct word rows per stretch)")
@@ -57,7 +58,7 @@ if args.reorder:
     from pytextgcn_amd import reorder_documents
     g, perm = reorder_documents(g)     # same graph, other numbering: the loop below addresses nodes through the masks only
 
-gcn = GCN(g.x.shape[1], len(np.unique(y)), n_hidden_gcn=n_hidden, dropout=dropout)   # :80
+gcn = GCN(g.x.shape[1], len(np.unique(y)), n_hidden_gcn=n_hidden, dropout=dropout, apply_activation=args.relu)   # :80
 criterion = th.nn.CrossEntropyLoss(reduction="mean")                   # :82
 device = th.device("cuda")                                             # :84
 gcn = gcn.to(device).float()                                           # :85

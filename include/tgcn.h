@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define TGCN_ABI_VERSION 6
+#define TGCN_ABI_VERSION 7
 
 enum {
     TGCN_OK = 0,
@@ -185,6 +185,28 @@ int tgcn_spmm_split(const tgcn_plan *plan, int transpose, const float *X, int64_
 int tgcn_spmm_acc(const tgcn_plan *plan, int transpose, const float *X, int64_t ldx, const float *X2, int64_t ldx2,
                   int64_t split, int F, float *Y, int64_t ldy, void *workspace, size_t workspace_bytes,
                   tgcn_stream stream);
+
+/* tgcn_spmm_act -- tgcn_spmm with an activation applied to M(^T) X + bias in the epilogue:
+ *       Y[r, 0:F] = act( sum_j M(^T)[row_begin + r, j] * X[j, 0:F]  (+ bias[0:F]) )
+ * The reference constructs `self.activation` and comments its call out (textgcn/lib/models.py:9,22); this is that line
+ * restored at no extra traffic -- the finished row is in registers when the bias is added.  act = TGCN_ACT_RELU stores
+ * v < 0 ? 0 : v (a NaN goes through, as torch.relu does): the same sums in the same order as tgcn_spmm and one select, so
+ * the result equals relu(tgcn_spmm(...)) bit for bit; act = TGCN_ACT_NONE IS tgcn_spmm.  Any other value: TGCN_E_INVALID.
+ * Same argument checks, same workspace (tgcn_spmm_workspace_bytes) as tgcn_spmm. */
+enum { TGCN_ACT_NONE = 0, TGCN_ACT_RELU = 1 };
+int tgcn_spmm_act(const tgcn_plan *plan, int transpose, const float *X, int64_t ldx, int F, const float *bias, int act,
+                  float *Y, int64_t ldy, void *workspace, size_t workspace_bytes, tgcn_stream stream);
+
+/* tgcn_act_grad -- the backward of that activation, in place:  G[r, c] <- A[r, c] > 0 ? G[r, c] : 0  for the [n_rows, F]
+ * gradient G (stride ldg) and A (stride lda) the activation tgcn_spmm_act STORED: relu(a) > 0 <=> a > 0, so the output is
+ * its own gate and neither a mask nor the pre-activation is kept.  colsum != NULL: also colsum[c] = sum_r of the GATED
+ * G[r, c] -- the bias gradient of the layer (the autograd of `out += bias` under the activation) -- from the registers
+ * that hold each row, in tgcn_colsum's fixed order (no atomics: reproducible run to run).  act = TGCN_ACT_NONE leaves G
+ * as it is (colsum is then tgcn_colsum's).  float4 lanes when F, lda, ldg are multiples of 4 and A, G 16-byte aligned,
+ * scalar lanes otherwise (same results); row offsets are 64-bit.  The workspace is needed only with colsum. */
+size_t tgcn_act_grad_workspace_bytes(int64_t n_rows, int F);
+int tgcn_act_grad(int act, const float *A, int64_t lda, float *G, int64_t ldg, int64_t n_rows, int F, float *colsum,
+                  void *workspace, size_t workspace_bytes, tgcn_stream stream);
 
 /* tgcn_spmm_adam -- tgcn_spmm whose result rows are never stored: row r of M(^T) @ G is the GRADIENT of row r of
  * `param` and is spent at once on torch.optim.Adam's update of that row (the arithmetic of tgcn_adam_step, op for

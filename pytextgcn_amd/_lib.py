@@ -12,11 +12,12 @@ from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64
 
 from .build import LIB_PATH
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 OK, E_INVALID, E_RANGE, E_HIP, E_NOMEM, E_WORKSPACE = 0, -1, -2, -3, -4, -5
 NORM_OFF, NORM_ACCURATE, NORM_REFERENCE = 0, 1, 2          # `normalize` of tgcn_plan_create
 DEGREE_ACCURATE, DEGREE_REFERENCE = 0, 1                   # `degree_sum` of tgcn_gcn_norm
+ACT_NONE, ACT_RELU = 0, 1                                   # `act` of tgcn_spmm_act / tgcn_act_grad
 DEGREE_SUMS = {"accurate": DEGREE_ACCURATE, "reference": DEGREE_REFERENCE}
 
 (Q_N_NODES, Q_N_ROWS, Q_NNZ, Q_NNZ_T, Q_SYMMETRIC, Q_ITEMS, Q_ITEMS_T, Q_LONG_ROWS, Q_LONG_ROWS_T,
@@ -44,6 +45,11 @@ SIGNATURES = {
                                 c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
     "tgcn_spmm_acc": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int,
                               c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
+    "tgcn_spmm_act": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int64,
+                              c_void_p, c_size_t, c_void_p]),
+    "tgcn_act_grad_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "tgcn_act_grad": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_size_t,
+                              c_void_p]),
     "tgcn_spmm_adam": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_int64, c_double, c_double, c_double, c_double, c_double, c_int64, c_void_p,
                                c_void_p, c_size_t, c_void_p]),

@@ -15,8 +15,8 @@ from typing import Optional
 import torch
 from torch import Tensor, nn
 
-from . import dense
-from .plan import GraphPlan, colsum, known_nonzero_rows, padded_base, plan_for
+from . import _lib, dense
+from .plan import GraphPlan, _known_colsum, colsum, known_nonzero_rows, padded_base, plan_for, relu_grad_
 
 
 def _fused_optimizer_for(param):
@@ -56,26 +56,34 @@ class _Propagate(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out: Tensor):
-        plan, F = ctx.plan, ctx.F
-        F4 = (F + 3) & ~3
-        g = _pad_cols(grad_out, F4).contiguous()
-        d_xw = d_bias = None
-        if ctx.needs_input_grad[1]:
-            p = getattr(ctx, "fused_param", None)
-            opt = _fused_optimizer_for(p) if p is not None else None
-            if opt is not None and F4 == F and opt._fused_update(p, plan, g):
-                d_xw = None                       # spent on the optimizer row by row, never stored
-            else:
-                # a gradient whose producer knows which rows are exactly zero (the fused cross-entropy: every row outside
-                # the loss mask) runs on M^T restricted to the other columns: the same sums without the zero terms
-                keep = known_nonzero_rows(g)
-                op = plan.transposed_on_rows(keep) if keep is not None else None
-                d_xw = op.spmm(g) if op is not None else plan.spmm(g, None, transpose=True)
-                if F4 != F:
-                    d_xw = d_xw[:, :F]
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            d_bias = colsum(g)[:F]
-        return None, d_xw, d_bias
+        F4 = (ctx.F + 3) & ~3
+        return _propagate_backward(ctx, _pad_cols(grad_out, F4).contiguous())
+
+
+def _propagate_backward(ctx, g: Tensor, d_bias: Optional[Tensor] = None):
+    """The backward of out = M @ xw + bias for `g` = d out, padded to whole float4 rows and contiguous.  `d_bias`: the
+    column sums of `g` when the caller already holds them (the activation's gate takes them in its own pass)."""
+    plan, F = ctx.plan, ctx.F
+    F4 = (F + 3) & ~3
+    d_xw = None
+    if ctx.needs_input_grad[1]:
+        p = getattr(ctx, "fused_param", None)
+        opt = _fused_optimizer_for(p) if p is not None else None
+        if opt is not None and F4 == F and opt._fused_update(p, plan, g):
+            d_xw = None                       # spent on the optimizer row by row, never stored
+        else:
+            # a gradient whose producer knows which rows are exactly zero (the fused cross-entropy: every row outside
+            # the loss mask) runs on M^T restricted to the other columns: the same sums without the zero terms
+            keep = known_nonzero_rows(g)
+            op = plan.transposed_on_rows(keep) if keep is not None else None
+            d_xw = op.spmm(g) if op is not None else plan.spmm(g, None, transpose=True)
+            if F4 != F:
+                d_xw = d_xw[:, :F]
+    if not (ctx.has_bias and ctx.needs_input_grad[2]):
+        d_bias = None
+    elif d_bias is None:
+        d_bias = colsum(g)[:F]
+    return None, d_xw, d_bias
 
 
 class _PropagateCached(torch.autograd.Function):
@@ -95,10 +103,63 @@ class _PropagateCached(torch.autograd.Function):
         return None, d_xw, d_bias, None
 
 
-def propagate(plan: GraphPlan, xw: Tensor, bias: Optional[Tensor]) -> Tensor:
+class _PropagateRelu(torch.autograd.Function):
+    """out = relu(M @ xw + bias) with the activation in the SpMM's epilogue (`tgcn_spmm_act`) -- the call the reference
+    comments out at textgcn/lib/models.py:22, restored.  Only the OUTPUT is kept for the backward: relu(a) > 0 <=> a > 0, so
+    it is its own gate.  The backward gates the incoming gradient and takes the bias gradient in one pass
+    (`tgcn_act_grad`), then goes on as `_Propagate.backward` does, W1's update inside the backward SpMM included.
+    `value`: the forward value computed earlier from the same (plan, xw, bias) versions (activation reuse).
+
+    The gate edits the incoming gradient IN PLACE when a kernel of this package produced it (the input-gradient GEMM of the
+    next layer: nobody else holds that buffer; a `retain_grad()` on the activated output would see the gated values), and a
+    copy of it otherwise."""
+
+    @staticmethod
+    def forward(ctx, plan: GraphPlan, xw: Tensor, bias: Optional[Tensor], value: Optional[Tensor] = None):
+        F = xw.size(1)
+        F4 = (F + 3) & ~3
+        if value is None:
+            out = plan.spmm(_pad_cols(xw.detach(), F4), None if bias is None else _pad_cols(bias.detach(), F4),
+                            activation=_lib.ACT_RELU)
+            ret = out if F4 == F else out[:, :F]       # (pad columns: relu(0 + 0) = 0)
+        else:
+            out = ret = value.detach()
+        ctx.plan = plan
+        ctx.F = F
+        ctx.has_bias = bias is not None
+        ctx.fused_param = xw if (isinstance(xw, nn.Parameter) and _fused_optimizer_for(xw) is not None) else None
+        ctx.save_for_backward(out)
+        return ret
+
+    @staticmethod
+    def backward(ctx, grad_out: Tensor):
+        (a,) = ctx.saved_tensors
+        F4 = (ctx.F + 3) & ~3
+        g = _pad_cols(grad_out, F4).contiguous()
+        if g.data_ptr() == grad_out.data_ptr() and _known_colsum(grad_out) is None:
+            g = g.clone()                            # somebody else's tensor: gate a copy
+        if a.size(1) != F4:
+            a = _pad_cols(a, F4)                     # (a reused value of an odd width: the pad columns gate nothing)
+        want_db = ctx.has_bias and ctx.needs_input_grad[2]
+        d_bias = relu_grad_(a, g, want_colsum=want_db)
+        return _propagate_backward(ctx, g, d_bias[:ctx.F] if want_db else None) + (None,)
+
+
+def _is_fused_activation(activation) -> bool:
+    """Exactly `nn.ReLU` runs in the SpMM epilogue; any other module is called on the layer's output."""
+    return type(activation) is nn.ReLU
+
+
+def propagate(plan: GraphPlan, xw: Tensor, bias: Optional[Tensor], activation: Optional[nn.Module] = None) -> Tensor:
+    """M @ xw + bias; with `activation` that module applied to it -- `nn.ReLU` inside the SpMM kernel (same bits as
+    `torch.relu` of the plain result), any other module by calling it (torch's kernels and autograd)."""
     if plan.n_rows != plan.num_nodes:
         raise ValueError("propagate() needs a whole-graph plan; use pytextgcn_amd.sharded for row blocks")
-    return _Propagate.apply(plan, xw, bias)
+    if activation is None:
+        return _Propagate.apply(plan, xw, bias)
+    if _is_fused_activation(activation):
+        return _PropagateRelu.apply(plan, xw, bias, None)
+    return activation(_Propagate.apply(plan, xw, bias))
 
 
 # Opt-in activation reuse.  In the reference's loop (flat_amazon.py:99-109) the eval forward of epoch k
@@ -251,32 +312,42 @@ class GCNConv(nn.Module):
                 self.bias.zero_()
 
     def forward(self, x: Tensor, edge_index: Tensor, edge_weight: Optional[Tensor] = None,
-                input_dropout: float = 0.0, rows: Optional[Tensor] = None) -> Tensor:
+                input_dropout: float = 0.0, rows: Optional[Tensor] = None,
+                activation: Optional[nn.Module] = None) -> Tensor:
         """`input_dropout` > 0 (an extension used by pytextgcn_amd.models.GCN when fused dropout is
         enabled): the layer sees dropout(x, p) -- training-mode inverted dropout -- fused into x @ W.
         `rows` (an extension; a bool mask over the nodes, a tensor the caller KEEPS: the restricted operator is cached
         under it): only these rows of the result will be read -- the propagate step runs on the operator restricted to
-        them (GraphPlan.on_rows); every other row comes back holding the bias."""
+        them (GraphPlan.on_rows); every other row comes back holding the bias.
+        `activation` (an extension; pytextgcn_amd.models.GCN(apply_activation=True) passes its module): applied to the
+        layer's output -- `nn.ReLU` in the epilogue of the SpMM kernel and gated in one pass on the way back (no extra
+        trip over the N x h activation; bit for bit `torch.relu(layer(x))`), any other module by calling it."""
         plan = self.plan(x, edge_index, edge_weight)
         if rows is not None:
             plan = plan.on_rows(rows) or plan
         if input_dropout > 0.0:
             if x.is_sparse:
                 raise ValueError("input_dropout applies to dense activations")
-            return propagate(plan, dense.xw_dropout(x, self.weight, input_dropout), self.bias)
+            return propagate(plan, dense.xw_dropout(x, self.weight, input_dropout), self.bias, activation)
         if _REUSE and x.is_sparse and x.size(1) == self.in_channels and is_sparse_identity(x):
             # layer 1 of TextGCN: one-hot features, X @ W1 is W1; keep M @ W1 + b1 while W1, b1 are unchanged
+            # (with the ReLU in the kernel's epilogue the kept value is the post-ReLU one -- the entry says which it holds;
+            # any other activation module is applied to the kept pre-activation value)
             key = _reuse_key(plan, self.weight, self.bias)
+            relu = _is_fused_activation(activation)
+            after = None if (relu or activation is None) else activation
             hit = getattr(self, "_reuse_cache", None)
-            if hit is not None and hit[0] == key and hit[2] is plan:   # `is`: an id() can be recycled
+            if hit is not None and hit[0] == key and hit[2] is plan and hit[3] == relu:   # `is`: an id() can be recycled
                 if torch.is_grad_enabled() and (self.weight.requires_grad or
                                                 (self.bias is not None and self.bias.requires_grad)):
-                    return _PropagateCached.apply(plan, self.weight, self.bias, hit[1])
-                return hit[1].detach()
-            out = propagate(plan, self.weight, self.bias)
-            self._reuse_cache = (key, out.detach(), plan)
-            return out
-        return propagate(plan, self.features_times(x, self.weight), self.bias)
+                    out = (_PropagateRelu if relu else _PropagateCached).apply(plan, self.weight, self.bias, hit[1])
+                else:
+                    out = hit[1].detach()
+                return out if after is None else after(out)
+            out = propagate(plan, self.weight, self.bias, activation if relu else None)
+            self._reuse_cache = (key, out.detach(), plan, relu)
+            return out if after is None else after(out)
+        return propagate(plan, self.features_times(x, self.weight), self.bias, activation)
 
     def plan(self, x: Tensor, edge_index: Tensor, edge_weight: Optional[Tensor] = None) -> GraphPlan:
         loops = (2 if self.improved else 1) if self.add_self_loops else 0     # fill weight of added loops

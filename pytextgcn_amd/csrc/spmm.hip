@@ -32,6 +32,9 @@ namespace {
 
 typedef float native_f4 __attribute__((ext_vector_type(4)));
 
+// The activation of the epilogue (tgcn_spmm_act, TGCN_ACT_RELU): torch.relu's value -- a NaN goes through
+__device__ __forceinline__ float relu1(float v) { return v < 0.f ? 0.f : v; }
+
 template <int VEC>
 struct Vec;
 template <>
@@ -54,6 +57,9 @@ struct Vec<4> {
     }
     static __device__ __forceinline__ type add(const type &a, const type &b) {
         return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+    }
+    static __device__ __forceinline__ type relu(const type &a) {
+        return make_float4(relu1(a.x), relu1(a.y), relu1(a.z), relu1(a.w));
     }
 };
 typedef float native_f2 __attribute__((ext_vector_type(2)));
@@ -83,6 +89,7 @@ struct Vec<1> {
     static __device__ __forceinline__ type zero() { return 0.f; }
     static __device__ __forceinline__ void fma(type &a, float v, const type &x) { a = fmaf(v, x, a); }
     static __device__ __forceinline__ type add(const type &a, const type &b) { return a + b; }
+    static __device__ __forceinline__ type relu(const type &a) { return relu1(a); }
 };
 
 __device__ __forceinline__ int readlane_i(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
@@ -136,7 +143,9 @@ __device__ __forceinline__ void adam_update(const AdamRow &ad, int64_t off, cons
 // ACC (tgcn_spmm_acc): the finished sum is ADDED to the row already in Y, and a row without stored entries is neither
 // read nor written -- the column-block launches of the pipelined exchange (pytextgcn_amd/sharded.py) each touch only the
 // rows they have entries for.  Rows are wave-owned and launches stream-ordered, so the result stays deterministic.
-template <int VEC, int U, int POLICY, bool ADAM = false, bool ACC = false>
+// RELU (tgcn_spmm_act): the row that is stored is relu(sum + bias) -- a select per element on registers that are about to
+// be written anyway.  A segment's partial sum stays as it is: its row is completed, and activated, by k_spmm_fix.
+template <int VEC, int U, int POLICY, bool ADAM = false, bool ACC = false, bool RELU = false>
 __device__ __forceinline__ void spmm_item(
     const WorkItem it, const int lane, const int col0, const int F,
     const int32_t *__restrict__ rowptr, const int2 *__restrict__ cv, const float *__restrict__ X,
@@ -145,6 +154,8 @@ __device__ __forceinline__ void spmm_item(
     float *__restrict__ carry, const int64_t ldc, const AdamRow ad = AdamRow{}) {
     static_assert(!ADAM || VEC == 4, "the fused optimizer epilogue is written for float4 lanes");
     static_assert(!(ADAM && ACC), "the optimizer epilogue consumes the row: nothing to accumulate into");
+    static_assert(!(RELU && (ADAM || ACC)), "the activation belongs to a row that is stored complete: a gradient row is not "
+                                            "activated, a partial sum cannot be");
     using V = Vec<VEC>;
     using vec_t = typename V::type;
     const int nvec = (min(F - col0, 64 * VEC) + VEC - 1) / VEC;  // vectors in this column tile
@@ -209,6 +220,8 @@ __device__ __forceinline__ void spmm_item(
                 if (active) *reinterpret_cast<vec_t *>(dst) = V::add(*reinterpret_cast<const vec_t *>(dst), acc);
             }
             touched = false;
+        } else if constexpr (RELU) {
+            store_row(Y + int64_t(r) * ldy + lc, V::relu(V::add(acc, bvec)));
         } else {
             store_row(Y + int64_t(r) * ldy + lc, V::add(acc, bvec));
         }
@@ -270,7 +283,7 @@ __device__ __forceinline__ void spmm_item(
 }
 
 // grid.x = ceil(n_items / 4), grid.y = column tiles of 64*VEC floats; one item per wavefront
-template <int VEC, int U, int POLICY, bool ACC = false>
+template <int VEC, int U, int POLICY, bool ACC = false, bool RELU = false>
 __global__ __launch_bounds__(256) void k_spmm_gather(
     const WorkItem *__restrict__ items, int n_items, const int32_t *__restrict__ rowptr,
     const int2 *__restrict__ cv, const float *__restrict__ X, int64_t ldx,
@@ -280,7 +293,7 @@ __global__ __launch_bounds__(256) void k_spmm_gather(
     const int item_id =
         __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));
     if (item_id >= n_items) return;
-    spmm_item<VEC, U, POLICY, false, ACC>(items[item_id], lane, blockIdx.y * (64 * VEC), F, rowptr, cv, X, ldx, X2, ldx2,
+    spmm_item<VEC, U, POLICY, false, ACC, RELU>(items[item_id], lane, blockIdx.y * (64 * VEC), F, rowptr, cv, X, ldx, X2, ldx2,
                                           split, bias, Y, ldy, carry, ldc);
 }
 
@@ -321,7 +334,7 @@ typedef float pk_f2 __attribute__((ext_vector_type(2)));
 constexpr unsigned kOobOffset = 0xFFFFF000u;
 static_assert(kOobOffset > 0xFFFF0000u && kOobOffset + 63u * 16u > kOobOffset, "padding offset must stay out of bounds");
 
-template <int G, int U, bool ACC = false>
+template <int G, int U, bool ACC = false, bool RELU = false>
 __global__ __launch_bounds__(256) void k_spmm_subb(
     const WorkItem *__restrict__ items, int n_items,
     const int2 *__restrict__ cv, const float *__restrict__ X, unsigned ldx4 /* row stride in bytes */,
@@ -329,6 +342,7 @@ __global__ __launch_bounds__(256) void k_spmm_subb(
     float *__restrict__ carry, int64_t ldc, const int4 *__restrict__ row_info) {
     constexpr int S = 64 / G;
     static_assert(G % U == 0, "a batch of G entries is gathered in whole groups of U");
+    static_assert(!(RELU && ACC), "a partial sum cannot be activated");
     const int lane = threadIdx.x & 63;
     const int item_id =
         __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));
@@ -412,9 +426,9 @@ __global__ __launch_bounds__(256) void k_spmm_subb(
                 }
                 continue;
             }
-            if (active)
-                *reinterpret_cast<float4 *>(Y + int64_t(r) * ldy + lane_off / 4) =
-                    make_float4(acc.x + bvec.x, acc.y + bvec.y, acc.z + bvec.z, acc.w + bvec.w);
+            float4 y = make_float4(acc.x + bvec.x, acc.y + bvec.y, acc.z + bvec.z, acc.w + bvec.w);
+            if constexpr (RELU) y = Vec<4>::relu(y);
+            if (active) *reinterpret_cast<float4 *>(Y + int64_t(r) * ldy + lane_off / 4) = y;
         }
     }
 }
@@ -512,12 +526,14 @@ __global__ __launch_bounds__(64 * kHotWaves) void k_spmm_hot(
 
 // One workgroup per long row: Y[row] = bias + carry[slot_begin] + ... + carry[slot_begin+count-1].
 // Wave w adds slots w, w+4, ...; the four partials are combined through LDS in wave order.
-template <int VEC, bool ADAM = false, bool ACC = false>
+// RELU: the completed row is activated here (long rows and the hot block's rows; see spmm_item).
+template <int VEC, bool ADAM = false, bool ACC = false, bool RELU = false>
 __global__ __launch_bounds__(256) void k_spmm_fix(const FixEntry *__restrict__ fix,
                                                   const float *__restrict__ carry, int64_t ldc,
                                                   const float *__restrict__ bias,
                                                   float *__restrict__ Y, int64_t ldy, int F,
                                                   const AdamRow ad = AdamRow{}) {
+    static_assert(!(RELU && (ADAM || ACC)), "the activation is not combined with the optimizer or the accumulate form");
     using V = Vec<VEC>;
     using vec_t = typename V::type;
     __shared__ vec_t red[kWavesPerBlock][64];
@@ -563,6 +579,7 @@ __global__ __launch_bounds__(256) void k_spmm_fix(const FixEntry *__restrict__ f
         } else {
             vec_t *dst = reinterpret_cast<vec_t *>(Y + int64_t(fe.row) * ldy + lc);
             if constexpr (ACC) t = V::add(*dst, t);            // (a long row always holds entries)
+            if constexpr (RELU) t = V::relu(t);
             *dst = t;
         }
     }
@@ -577,11 +594,12 @@ void launch_hot(const CsrBlock &b, const float *X, int64_t ldx, const float *X2,
 }
 
 // `ad` != nullptr (VEC == 4 only): the finished rows are spent on the optimizer instead of being stored in Y;
-// `acc`: the accumulate form (Y += M X on the rows that hold entries; no bias)
+// `acc`: the accumulate form (Y += M X on the rows that hold entries; no bias); `relu`: the stored rows are activated
+// (neither with `ad` nor with `acc`: checked by the callers)
 template <int VEC>
 int launch_vec(const CsrBlock &blk, const float *X, int64_t ldx, const float *X2, int64_t ldx2, int split,
                int F, const float *bias, float *Y, int64_t ldy, float *carry, hipStream_t stream,
-               const AdamRow *ad = nullptr, const bool acc = false) {
+               const AdamRow *ad = nullptr, const bool acc = false, const bool relu = false) {
     const int tiles = (F + 64 * VEC - 1) / (64 * VEC);
     const int64_t ldc = round_up4(F);
     // With a dense hot block the float4 kernels run on the partition without the hot rows, next to
@@ -628,7 +646,13 @@ int launch_vec(const CsrBlock &blk, const float *X, int64_t ldx, const float *X2
             // 8 / 16 measured 8 % / 6 % slower at F = 64 (c4), document rows hold ~10 entries and every started
             // group of U is gathered in full (with the rows of a block sorted by degree 2 / 8 measured 10 % / 8 % slower)
             const unsigned ldx4 = static_cast<unsigned>(ldx * 4), xb = static_cast<unsigned>(x_extent);
-            if (F <= 64 && !acc)
+            if (relu && F <= 64)
+                k_spmm_subb<16, 4, false, true><<<grid, 256, 0, stream>>>(b.items, b.n_items, cv, X, ldx4, xb, F, bias, Y, ldy,
+                                                                         carry, ldc, blk.row_info);
+            else if (relu)
+                k_spmm_subb<32, 4, false, true><<<grid, 256, 0, stream>>>(b.items, b.n_items, cv, X, ldx4, xb, F, bias, Y, ldy,
+                                                                         carry, ldc, blk.row_info);
+            else if (F <= 64 && !acc)
                 k_spmm_subb<16, 4><<<grid, 256, 0, stream>>>(b.items, b.n_items, cv, X, ldx4, xb, F, bias, Y, ldy, carry, ldc,
                                                             blk.row_info);
             else if (F <= 64)
@@ -648,6 +672,10 @@ int launch_vec(const CsrBlock &blk, const float *X, int64_t ldx, const float *X2
                 constexpr int P = VEC == 4 ? 1 : 0;
                 k_spmm_gather<VEC, 8, P, true><<<grid, 256, 0, stream>>>(b.items, b.n_items, rowptr, cv, X, ldx, X2, ldx2, split,
                                                                          F, bias, Y, ldy, carry, ldc);
+            } else if (relu) {
+                constexpr int P = VEC == 4 ? 3 : 0;
+                k_spmm_gather<VEC, 8, P, false, true><<<grid, 256, 0, stream>>>(b.items, b.n_items, rowptr, cv, X, ldx, X2, ldx2,
+                                                                                split, F, bias, Y, ldy, carry, ldc);
             } else if constexpr (VEC == 4)
                 k_spmm_gather<4, 8, 3><<<grid, 256, 0, stream>>>(b.items, b.n_items, rowptr, cv, X, ldx, X2, ldx2, split, F,
                                                                  bias, Y, ldy, carry, ldc);
@@ -663,6 +691,8 @@ int launch_vec(const CsrBlock &blk, const float *X, int64_t ldx, const float *X2
             if constexpr (VEC == 4) k_spmm_fix<4, true><<<grid, 256, 0, stream>>>(b.fix, carry, ldc, bias, nullptr, 0, F, *ad);
         } else if (acc) {
             k_spmm_fix<VEC, false, true><<<grid, 256, 0, stream>>>(b.fix, carry, ldc, bias, Y, ldy, F);
+        } else if (relu) {
+            k_spmm_fix<VEC, false, false, true><<<grid, 256, 0, stream>>>(b.fix, carry, ldc, bias, Y, ldy, F);
         } else {
             k_spmm_fix<VEC><<<grid, 256, 0, stream>>>(b.fix, carry, ldc, bias, Y, ldy, F);
         }
@@ -674,7 +704,7 @@ int launch_vec(const CsrBlock &blk, const float *X, int64_t ldx, const float *X2
 }  // namespace
 
 int launch_spmm(const CsrBlock &b, const float *X, int64_t ldx, const float *X2, int64_t ldx2, int split,
-                int F, const float *bias, float *Y, int64_t ldy, float *carry, hipStream_t stream, bool acc) {
+                int F, const float *bias, float *Y, int64_t ldy, float *carry, hipStream_t stream, bool acc, int act) {
     if (X2 == nullptr) {  // single operand
         X2 = X;
         ldx2 = ldx;
@@ -684,8 +714,9 @@ int launch_spmm(const CsrBlock &b, const float *X, int64_t ldx, const float *X2,
                             reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(bias) |
                             reinterpret_cast<uintptr_t>(carry);
     const bool vec4 = (F % 4 == 0) && (ldx % 4 == 0) && (ldx2 % 4 == 0) && (ldy % 4 == 0) && (align % 16 == 0);
-    return vec4 ? launch_vec<4>(b, X, ldx, X2, ldx2, split, F, bias, Y, ldy, carry, stream, nullptr, acc)
-                : launch_vec<1>(b, X, ldx, X2, ldx2, split, F, bias, Y, ldy, carry, stream, nullptr, acc);
+    const bool relu = act == TGCN_ACT_RELU;
+    return vec4 ? launch_vec<4>(b, X, ldx, X2, ldx2, split, F, bias, Y, ldy, carry, stream, nullptr, acc, relu)
+                : launch_vec<1>(b, X, ldx, X2, ldx2, split, F, bias, Y, ldy, carry, stream, nullptr, acc, relu);
 }
 
 // the SpMM whose rows feed the optimizer (tgcn_spmm_adam); float4 path only, checked by the caller
@@ -699,10 +730,10 @@ int launch_spmm_adam(const CsrBlock &b, const float *X, int64_t ldx, const float
     return launch_vec<4>(b, X, ldx, X2, ldx2, split, F, nullptr, nullptr, 0, carry, stream, &ad);
 }
 
-// tgcn_spmm_split / tgcn_spmm_acc behind one set of argument checks (below)
+// tgcn_spmm_split / tgcn_spmm_acc / tgcn_spmm_act behind one set of argument checks (below)
 int spmm_entry(const tgcn_plan *plan, int transpose, const float *X, int64_t ldx, const float *X2, int64_t ldx2,
                int64_t split, int F, const float *bias, float *Y, int64_t ldy, void *workspace, size_t workspace_bytes,
-               tgcn_stream stream, bool acc);
+               tgcn_stream stream, bool acc, int act = TGCN_ACT_NONE);
 
 }  // namespace tgcn
 
@@ -806,13 +837,23 @@ int tgcn_spmm_acc(const tgcn_plan *plan, int transpose, const float *X, int64_t 
                             stream, true);
 }
 
+int tgcn_spmm_act(const tgcn_plan *plan, int transpose, const float *X, int64_t ldx, int F, const float *bias, int act,
+                  float *Y, int64_t ldy, void *workspace, size_t workspace_bytes, tgcn_stream stream) {
+    return tgcn::spmm_entry(plan, transpose, X, ldx, nullptr, 0, 0, F, bias, Y, ldy, workspace, workspace_bytes, stream,
+                            false, act);
+}
+
 }  // extern "C"
 
 namespace tgcn {
 
 int spmm_entry(const tgcn_plan *plan, int transpose, const float *X, int64_t ldx, const float *X2,
                int64_t ldx2, int64_t split, int F, const float *bias, float *Y, int64_t ldy,
-               void *workspace, size_t workspace_bytes, tgcn_stream stream, bool acc) {
+               void *workspace, size_t workspace_bytes, tgcn_stream stream, bool acc, int act) {
+    if (act != TGCN_ACT_NONE && act != TGCN_ACT_RELU) {
+        set_error("tgcn_spmm_act: unknown act %d (TGCN_ACT_NONE = 0, TGCN_ACT_RELU = 1)", act);
+        return TGCN_E_INVALID;
+    }
     if (!plan || !X || !Y) {
         set_error("tgcn_spmm: NULL plan/X/Y");
         return TGCN_E_INVALID;
@@ -846,7 +887,7 @@ int spmm_entry(const tgcn_plan *plan, int transpose, const float *X, int64_t ldx
     if (cur != plan->device) TGCN_HIP_CHECK(hipSetDevice(plan->device));
     const int st = launch_spmm(b, X, ldx, X2, ldx2, static_cast<int>(split), F, bias, Y, ldy,
                                need ? static_cast<float *>(workspace) : nullptr,
-                               static_cast<hipStream_t>(stream), acc);
+                               static_cast<hipStream_t>(stream), acc, act);
     if (cur != plan->device) (void)hipSetDevice(cur);
     return st;
 }

@@ -2,8 +2,14 @@
 
 Same constructor signature and defaults, same `layers` ModuleList (state_dict keys
 `layers.{i}.weight` (in, out) / `layers.{i}.bias`), same forward: dropout between layers, none
-after the last, and NO activation -- the reference's activation call is commented out
+after the last, and by default NO activation -- the reference's activation call is commented out
 (models.py:22) although `self.activation` is constructed (models.py:9); both facts are kept.
+
+`apply_activation=True` (an extension, last keyword) restores that line: `x = layer(x); x = activation(x);
+x = dropout(x)` between the layers, nothing after the last -- the two-layer GCN with a ReLU of Kipf & Welling and of
+the TextGCN paper.  `nn.ReLU` runs in the epilogue of the first layer's SpMM kernel (pytextgcn_amd/conv.py); any other
+module is called on the layer's output.  `pytextgcn_amd.sharded.ShardedGCN` has no such switch: its narrow exchange rests
+on the network being linear.
 """
 from __future__ import annotations
 
@@ -42,9 +48,10 @@ def enable_fused_dropout(on: bool = True) -> None:
 
 class GCN(nn.Module):
     def __init__(self, in_channels, out_channels, n_gcn=2, n_hidden_gcn=64, activation=nn.ReLU,
-                 dropout=0.5):
+                 dropout=0.5, apply_activation=False):
         super().__init__()
         self.activation = activation()
+        self.apply_activation = bool(apply_activation)
         self.dropout = dropout
         self.layers = nn.ModuleList([GCNConv(in_channels, n_hidden_gcn, add_self_loops=True)])
         for _ in range(n_gcn - 2):
@@ -74,14 +81,18 @@ class GCN(nn.Module):
         the validation and training rows in evaluation (:109-114).  The LAST layer's propagate step then runs on the
         operator restricted to them; every other row of the result holds the last layer's bias.  In a TextGCN graph the
         word rows, which nobody reads, hold two thirds of the operator's entries."""
-        if (_COLLAPSE and len(self.layers) > 1 and not torch.is_grad_enabled()
+        # (modules pickled before `apply_activation` existed do not carry it: they are the linear network)
+        act = self.activation if getattr(self, "apply_activation", False) else None
+        if (_COLLAPSE and act is None and len(self.layers) > 1 and not torch.is_grad_enabled()
                 and (not self.training or self.dropout == 0)):
-            return self._collapsed_forward(g, rows)
+            return self._collapsed_forward(g, rows)      # the identity it uses needs the LINEAR network
         x = g.x
         pending = 0.0                          # dropout still owed to x (fused into the next layer)
         last = len(self.layers) - 1
         for i, layer in enumerate(self.layers):
             kw = {"rows": rows} if (rows is not None and i == last) else {}
+            if act is not None and i < last:
+                kw["activation"] = act
             x = layer(x, g.edge_index, g.edge_attr, input_dropout=pending, **kw) if pending > 0.0 \
                 else layer(x, g.edge_index, g.edge_attr, **kw)
             pending = 0.0

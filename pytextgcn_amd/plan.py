@@ -247,11 +247,14 @@ class GraphPlan:
 
     # -- compute ----------------------------------------------------------------------------
     def spmm(self, x: Tensor, bias: Optional[Tensor] = None, transpose: bool = False,
-             out: Optional[Tensor] = None, x2: Optional[Tensor] = None, accumulate: bool = False) -> Tensor:
+             out: Optional[Tensor] = None, x2: Optional[Tensor] = None, accumulate: bool = False,
+             activation: int = _lib.ACT_NONE) -> Tensor:
         """out[r] = sum_j M(^T)[row_begin + r, j] x[j] (+ bias); x is [num_nodes, F] fp32.
         With `x2` the operand is split: columns [0, len(x)) read x, the remaining ones x2.
         `accumulate` (`tgcn_spmm_acc`): the sums are ADDED to `out` (required, no bias) on the rows that hold entries;
-        rows without entries are not touched."""
+        rows without entries are not touched.
+        `activation` (`tgcn_spmm_act`; `_lib.ACT_RELU`): applied to the finished rows in the kernel's epilogue -- bit for bit
+        `torch.relu` of the plain product; one operand buffer, not with `accumulate`."""
         _require_cuda(x, "x")
         if x.dtype != torch.float32 or x.dim() != 2:
             raise TypeError(f"spmm operand must be a 2-D float32 tensor, got {x.dtype} {tuple(x.shape)}")
@@ -280,6 +283,9 @@ class GraphPlan:
                 raise ValueError(f"bias has {bias.numel()} entries for F={F}")
         if accumulate and (out is None or bias is not None):
             raise ValueError("accumulate=True adds into `out` (required) and takes no bias")
+        if activation != _lib.ACT_NONE and (accumulate or x2 is not None):
+            raise ValueError("activation= goes with one operand buffer and without accumulate=True (a partial sum cannot be "
+                             "activated)")
         if out is None:
             out = torch.empty(n_out, F, dtype=torch.float32, device=x.device)
         elif out.shape != (n_out, F) or out.dtype != torch.float32 or out.stride(1) != 1 or out.device != x.device:
@@ -291,6 +297,12 @@ class GraphPlan:
                 self._h, int(transpose), x.data_ptr(), x.stride(0),
                 x2.data_ptr() if x2 is not None else None, x2.stride(0) if x2 is not None else 0, split, F,
                 out.data_ptr(), out.stride(0), ws.data_ptr() if ws is not None else None, ws_bytes, _stream_ptr(x.device)))
+            return out
+        if activation != _lib.ACT_NONE:
+            _lib.check(self._lib.tgcn_spmm_act(
+                self._h, int(transpose), x.data_ptr(), x.stride(0), F, bias.data_ptr() if bias is not None else None,
+                int(activation), out.data_ptr(), out.stride(0), ws.data_ptr() if ws is not None else None, ws_bytes,
+                _stream_ptr(x.device)))
             return out
         _lib.check(self._lib.tgcn_spmm_split(
             self._h, int(transpose), x.data_ptr(), x.stride(0),
@@ -452,6 +464,35 @@ def colsum(g: Tensor) -> Tensor:
     _lib.check(lib.tgcn_colsum(g.data_ptr(), g.stride(0), n, F, out.data_ptr(), ws.data_ptr(),
                                ws.numel(), _stream_ptr(g.device)))
     return out
+
+
+def forget_colsum(t: Tensor) -> None:
+    """Drop the note a producer left for `t`: a kernel of this package is about to edit `t` in place behind torch's back
+    (no version bump), so the noted sums would be those of another matrix."""
+    _KNOWN_COLSUMS.pop(t.data_ptr(), None)
+
+
+def relu_grad_(a: Tensor, g: Tensor, want_colsum: bool = False) -> Optional[Tensor]:
+    """g[r, c] <- a[r, c] > 0 ? g[r, c] : 0 IN PLACE (`tgcn_act_grad`): the backward of the ReLU fused into the SpMM epilogue,
+    `a` the activation that launch stored.  `want_colsum`: returns the column sums of the gated g (the layer's bias
+    gradient) taken in the same pass, in `colsum`'s deterministic order.  Any column-sum note of `g` is dropped: it
+    described the matrix before the gate."""
+    lib = _lib.load()
+    _require_cuda(g, "g")
+    if a.shape != g.shape or a.dim() != 2 or a.dtype != torch.float32 or g.dtype != torch.float32 or a.device != g.device \
+            or (g.size(0) and (a.stride(1) != 1 or g.stride(1) != 1)):
+        raise TypeError("relu_grad_: activation and gradient must be float32 [n, F] device matrices of one shape with unit "
+                        "column stride")
+    forget_colsum(g)
+    n, F = g.shape
+    sums = ws = None
+    if want_colsum:
+        sums = torch.empty(F, dtype=torch.float32, device=g.device)
+        ws = torch.empty(max(lib.tgcn_act_grad_workspace_bytes(n, F), 16), dtype=torch.uint8, device=g.device)
+    _lib.check(lib.tgcn_act_grad(_lib.ACT_RELU, a.data_ptr(), a.stride(0), g.data_ptr(), g.stride(0), n, F,
+                                 sums.data_ptr() if sums is not None else None, ws.data_ptr() if ws is not None else None,
+                                 ws.numel() if ws is not None else 0, _stream_ptr(g.device)))
+    return sums
 
 
 # ------------------------------------------------------------------------------------------
