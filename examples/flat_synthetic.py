@@ -5,6 +5,10 @@ the host), same hyper-parameter names, on a synthetic corpus because the Amazon 
 not in the reference tree (.MISSING_LARGE_BLOBS:1-3).  Line references: flat_amazon.py.
 
     python examples/flat_synthetic.py [--docs 5000] [--epochs 50] [--fused] [--preset amazon|dbpedia]
+                                      [--model gcn|egcn] [--embedding-dim 2000]
+
+`--model egcn` trains the reference's embedding GCN instead (flat_amazon.py:79 carries its constructor one line from the live
+one: `EGCN(..., embedding_dim=2000, ...)`); `--fused` belongs to the GCN only (train.FlatLoop is not extended to EGCN).
 
 `--preset dbpedia` takes flat_dbpedia.py's settings instead (flat_dbpedia.py:20-34,70-71,80: dropout 0.5, max_df 0.4, window 5,
 documents cut to 15 tokens, hidden width 32, a separate validation split appended to the training documents) with a class count
@@ -21,7 +25,7 @@ from sklearn.metrics import accuracy_score, f1_score
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pytextgcn_amd import Text2GraphTransformer, synth  # noqa: E402
-from pytextgcn_amd.models import GCN  # noqa: E402
+from pytextgcn_amd.models import EGCN, GCN  # noqa: E402
 
 p = argparse.ArgumentParser()
 p.add_argument("--docs", type=int, default=5000)
@@ -32,7 +36,11 @@ p.add_argument("--relu", action="store_true", help="GCN(apply_activation=True): 
 p.add_argument("--reorder", action="store_true",
                help="pytextgcn_amd.reorder_documents: lay the document nodes out by clusters found from the graph (a corpus "
                     "with topical locality whose file is not sorted by class gathers fewer distinct word rows per stretch)")
+p.add_argument("--model", choices=["gcn", "egcn"], default="gcn", help="the network: textgcn.lib.models.GCN or .EGCN")
+p.add_argument("--embedding-dim", type=int, default=2000, help="EGCN(embedding_dim=...) (flat_amazon.py:79)")
 args = p.parse_args()
+if args.model == "egcn" and (args.fused or args.relu):
+    p.error("--fused and --relu belong to --model gcn")
 
 seed, lr, min_df = 44, 0.05, 5                                         # :22-35,66 (min_df 100 at DBpedia's 240 k documents)
 if args.preset == "amazon":
@@ -58,7 +66,10 @@ if args.reorder:
     from pytextgcn_amd import reorder_documents
     g, perm = reorder_documents(g)     # same graph, other numbering: the loop below addresses nodes through the masks only
 
-gcn = GCN(g.x.shape[1], len(np.unique(y)), n_hidden_gcn=n_hidden, dropout=dropout, apply_activation=args.relu)   # :80
+if args.model == "egcn":
+    gcn = EGCN(g.x.shape[1], len(np.unique(y)), embedding_dim=args.embedding_dim, n_hidden_gcn=n_hidden, dropout=dropout)   # :79
+else:
+    gcn = GCN(g.x.shape[1], len(np.unique(y)), n_hidden_gcn=n_hidden, dropout=dropout, apply_activation=args.relu)   # :80
 criterion = th.nn.CrossEntropyLoss(reduction="mean")                   # :82
 device = th.device("cuda")                                             # :84
 gcn = gcn.to(device).float()                                           # :85

@@ -395,6 +395,31 @@ int tgcn_gemm_nt_colsum(const float *A, int64_t lda, const float *B, int64_t ldb
                         size_t workspace_bytes, tgcn_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The front end of the reference's EGCN (textgcn/lib/models.py:28-52: `Linear(in_channels, embedding_dim)`, SELU, dropout,
+ * then the first GCNConv's x @ W) for TextGCN's one-hot features, as ONE product.  With x = I the Linear's output is
+ * E^T + b for its weight E [K, N] (K = embedding_dim, row-major as nn.Linear keeps it, leading dimension lde >= N; no
+ * alignment or padding is asked of it), so with
+ *       a(i, k) = s * keep(i, k) * selu(E[k, i] + b[k]),      s = 1 / (1 - p),
+ * keep(i, k) the decision of tgcn_gemm_*_dropout for mask row mask_row0 + i and column k (same hash, same threshold
+ * clamp, same one-element int64 device seed), and selu with torch's constants:
+ *   tgcn_embed_xw        C[i, 0:n]  = sum_k a(i, k) W[k, 0:n]                           C [N, n] stride ldc, W [K, n] stride ldw
+ *   tgcn_embed_xw_grad   dE[k, i]   = s keep(i, k) selu'(E[k, i] + b[k]) sum_j G[i, j] W[k, j]    (E's layout, stride ldde)
+ *                        db[k]      = sum_i dE[k, i]
+ *                        dW[k, j]   = sum_i a(i, k) G[i, j]                             G = dC [N, n] stride ldg
+ * The N x K activation is never stored: a is formed in registers on its way into the fp32 matrix cores, and recomputed
+ * (same mask) for dW.  p = 0 or seed = NULL: no mask, s = 1.  0 <= p < 1.  N >= 0, K >= 1, n >= 1; all offsets are 64-bit.
+ * Unlike tgcn_gemm_*_dropout these calls take the mask row offset as an argument and read no thread-local state.
+ * tgcn_embed_xw_grad: dE and db are computed together (both or neither), dW on its own; the workspace is needed for dW only
+ * and holds partial sums of dW, nothing of size N x K.  Fixed summation orders, no atomics: reproducible run to run. */
+int tgcn_embed_xw(const float *E, int64_t lde, const float *b, const float *W, int64_t ldw, float *C, int64_t ldc,
+                  int64_t N, int K, int n, double p, const uint64_t *seed, int64_t mask_row0, tgcn_stream stream);
+size_t tgcn_embed_xw_grad_workspace_bytes(int64_t N, int K, int n);
+int tgcn_embed_xw_grad(const float *E, int64_t lde, const float *b, const float *W, int64_t ldw, const float *G,
+                       int64_t ldg, float *dE, int64_t ldde, float *db, float *dW, int64_t lddw, int64_t N, int K, int n,
+                       double p, const uint64_t *seed, int64_t mask_row0, void *workspace, size_t workspace_bytes,
+                       tgcn_stream stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Word-word PMI edges (graph construction).  Replaces the reference's Cython
  * entry point `compute_word_word_edges(X, n_vocab, n_documents, seq_len, window_size, n_jobs, verbose)`
  * (textgcn/lib/clib/graphbuilder.pyx:23-25, called at text2graph.py:156-160) and its test hook

@@ -97,6 +97,12 @@ SIGNATURES = {
     "tgcn_gemm_nt_colsum_workspace_bytes": (c_size_t, [c_int]),
     "tgcn_gemm_nt_colsum": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int,
                                     c_double, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tgcn_embed_xw": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int,
+                              c_double, c_void_p, c_int64, c_void_p]),
+    "tgcn_embed_xw_grad_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "tgcn_embed_xw_grad": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                   c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_double, c_void_p, c_int64,
+                                   c_void_p, c_size_t, c_void_p]),
     "tgcn_wwedges_create": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p,
                                     POINTER(c_void_p)]),
     "tgcn_wwedges_query": (c_int, [c_void_p, c_int, POINTER(c_int64)]),

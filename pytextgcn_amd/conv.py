@@ -278,6 +278,20 @@ def sparse_times(x: Tensor, w: Tensor) -> Tensor:
     return _SparseTimesDense.apply(_feature_plan(x), w)
 
 
+def features_times(x: Tensor, w: Tensor, in_channels: int) -> Tensor:
+    """X @ w for the feature formats of text2graph.py:226-246 (`w` has `in_channels` rows): dense, the sparse identity,
+    [I | H] and general sparse COO.  Shared by `GCNConv` and by the embedding layer of `pytextgcn_amd.models.EGCN`."""
+    if not x.is_sparse:
+        return dense.xw(x, w)             # fp32 MFMA kernels for tall-skinny shapes
+    if x.size(1) != in_channels:
+        raise ValueError(f"x has {x.size(1)} features, the layer expects {in_channels}")
+    if is_sparse_identity(x):
+        return w
+    h = split_identity_block(x)
+    n = x.size(0)
+    return w[:n] + sparse_times(h, w[n:]) if h is not None else sparse_times(x, w)
+
+
 def glorot_(t: Tensor) -> Tensor:
     a = math.sqrt(6.0 / (t.size(-2) + t.size(-1)))
     with torch.no_grad():
@@ -355,15 +369,7 @@ class GCNConv(nn.Module):
 
     def features_times(self, x: Tensor, w: Tensor) -> Tensor:
         """X @ w for the feature formats of text2graph.py:226-246 (`w` has `in_channels` rows)."""
-        if not x.is_sparse:
-            return dense.xw(x, w)             # fp32 MFMA kernels for tall-skinny shapes
-        if x.size(1) != self.in_channels:
-            raise ValueError(f"x has {x.size(1)} features, the layer expects {self.in_channels}")
-        if is_sparse_identity(x):
-            return w
-        h = split_identity_block(x)
-        n = x.size(0)
-        return w[:n] + sparse_times(h, w[n:]) if h is not None else sparse_times(x, w)
+        return features_times(x, w, self.in_channels)
 
     def __getstate__(self):
         # th.save(gcn, ...) pickles the whole module (flat_amazon.py:128): cached activations and the

@@ -21,6 +21,7 @@
 #include <utility>
 
 #include "common.h"
+#include "drop_hash.h"
 
 namespace tgcn {
 namespace {
@@ -90,21 +91,8 @@ __device__ __forceinline__ int64_t drop_row_of(const Drop &d, int64_t row) {
 // word h * wph + q / 8.
 __host__ __device__ __forceinline__ int drop_bits_wph(int k) { return ((k + 7) / 8 + 7) / 8; }
 
-// The hash is split so that the expensive part is paid once per ROW and lane, not once per element: a row key
-// (murmur3 mixing of the 64-bit row index with the seed) and, per element, key + col * golden-ratio constant
-// through a two-multiply finaliser.  (The first version hashed row * ld + col per element: 4 quarter-rate
-// 32-bit multiplies and a 64-bit multiply-add each; profiles/r02_pmc_gemm_c4.md: 4x the vector-ALU instructions
-// of the plain kernels.)  All three GEMMs call the same two functions, so they regenerate the same mask.
-__device__ __forceinline__ uint32_t drop_row_key(uint32_t s_lo, uint32_t s_hi, int64_t row) {
-    uint32_t h = uint32_t(row) ^ s_lo;
-    h *= 0xcc9e2d51u;
-    h = (h << 15) | (h >> 17);
-    h *= 0x1b873593u;
-    h ^= uint32_t(uint64_t(row) >> 32) + s_hi;
-    h ^= h >> 16;
-    h *= 0x85ebca6bu;
-    return h;
-}
+// The hash itself (drop_row_key, drop_col_term, drop_hash_keep) lives in drop_hash.h: all three GEMMs -- and the fused
+// embedding kernels of embed.hip -- call the same functions, so they regenerate the same mask.
 
 // the same key for a row index that is the same in every lane of the wave (the LDS-staged tn kernels: a wave copies whole
 // rows): forced into scalar registers, so that the three multiplies run on the scalar unit instead of as quarter-rate
@@ -115,16 +103,8 @@ __device__ __forceinline__ uint32_t drop_row_key_uniform(uint32_t s_lo, uint32_t
     return drop_row_key(s_lo, s_hi, int64_t((uint64_t(hi) << 32) | lo));
 }
 
-__device__ __forceinline__ uint32_t drop_col_term(int col) { return uint32_t(col) * 0x9E3779B1u; }
-
 __device__ __forceinline__ bool drop_keep(uint32_t row_key, uint32_t col_term, const Drop &d) {
-    uint32_t h = row_key + col_term;
-    h ^= h >> 15;
-    h *= 0x2c1b3c6du;
-    h ^= h >> 12;
-    h *= 0x297a2d39u;
-    h ^= h >> 15;
-    return h >= d.thresh;
+    return drop_hash_keep(row_key, col_term, d.thresh);
 }
 
 __device__ __forceinline__ float drop_elem(float v, uint32_t row_key, uint32_t col_term, const Drop &d) {

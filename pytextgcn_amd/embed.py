@@ -1,0 +1,108 @@
+"""The front end of EGCN on one-hot features as one product (libtgcn.so `tgcn_embed_xw*`, pytextgcn_amd/csrc/embed.hip):
+`dropout(selu(Linear(I))) @ W` of textgcn/lib/models.py:43-47 without the N x embedding_dim activation.  With x = I the
+Linear's output is `E.t() + b` for its weight E [K, N]; the kernels form s * keep * selu(E[k, i] + b[k]) in registers on
+the way into the matrix cores, in the forward product and again (same mask, regenerated from an 8-byte seed) in the
+weight gradient.  The backward holds dE -- one N x K matrix, the gradient of the parameter -- and nothing else of that size."""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+from torch import Tensor
+
+from . import _lib
+from .dense import _check_seed, new_seed
+from .plan import _stream_ptr, alloc_padded
+
+
+def _require(E: Tensor, b: Tensor, W: Tensor) -> None:
+    """libtgcn.so only: anything else is an error, never a silent fallback."""
+    for name, t in (("E", E), ("b", b), ("W", W)):
+        if not t.is_cuda:
+            raise RuntimeError(f"pytextgcn_amd: the fused embedding product needs `{name}` on an AMD GPU (it lives on "
+                               f"{t.device}); there is no CPU fallback")
+        if t.dtype != torch.float32:
+            raise TypeError(f"pytextgcn_amd: the fused embedding product takes float32 operands, `{name}` is {t.dtype} "
+                            "(the reference casts the model with .float(), flat_amazon.py:85)")
+    if E.dim() != 2 or W.dim() != 2 or b.dim() != 1 or E.size(0) != b.size(0) or E.size(0) != W.size(0) \
+            or E.size(0) == 0 or W.size(1) == 0:
+        raise ValueError(f"embed_xw: E {tuple(E.shape)} (embedding_dim, N), b {tuple(b.shape)} and W {tuple(W.shape)} "
+                         "(embedding_dim, n) do not fit")
+
+
+def _unit_cols(t: Tensor) -> Tensor:
+    return t if (t.stride(1) == 1 and t.stride(0) >= t.size(1)) else t.contiguous()
+
+
+def embed_xw_forward(E: Tensor, b: Tensor, W: Tensor, p: float = 0.0, seed: Optional[Tensor] = None,
+                     out: Optional[Tensor] = None) -> Tensor:
+    """C [N, n] = dropout(selu(E.t() + b), p) @ W; `seed` None (or p = 0): no mask.  No autograd."""
+    lib = _lib.load()
+    E, W, b = _unit_cols(E), _unit_cols(W), b.contiguous()
+    K, N = E.shape
+    n = W.size(1)
+    c = alloc_padded(N, n, E.device) if out is None else out
+    if seed is not None:
+        _check_seed(seed, E.device)
+    _lib.check(lib.tgcn_embed_xw(E.data_ptr(), max(E.stride(0), N), b.data_ptr(), W.data_ptr(), W.stride(0), c.data_ptr(),
+                                 max(c.stride(0), n), N, K, n, float(p), seed.data_ptr() if seed is not None else None, 0,
+                                 _stream_ptr(E.device)))
+    return c
+
+
+def embed_xw_backward(E: Tensor, b: Tensor, W: Tensor, G: Tensor, p: float = 0.0, seed: Optional[Tensor] = None,
+                      want_e: bool = True, want_w: bool = True):
+    """(dE, db, dW) of `embed_xw_forward` for G = dC; a pair that is not wanted comes back as None."""
+    lib = _lib.load()
+    E, W, b, G = _unit_cols(E), _unit_cols(W), b.contiguous(), _unit_cols(G)
+    K, N = E.shape
+    n = W.size(1)
+    dE = torch.empty(K, N, dtype=torch.float32, device=E.device) if want_e else None
+    db = torch.empty(K, dtype=torch.float32, device=E.device) if want_e else None
+    dW = torch.empty(K, n, dtype=torch.float32, device=E.device) if want_w else None
+    if not (want_e or want_w):
+        return None, None, None
+    ws_bytes = lib.tgcn_embed_xw_grad_workspace_bytes(N, K, n) if want_w else 0
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=E.device)
+    if seed is not None:
+        _check_seed(seed, E.device)
+    _lib.check(lib.tgcn_embed_xw_grad(E.data_ptr(), max(E.stride(0), N), b.data_ptr(), W.data_ptr(), W.stride(0),
+                                      G.data_ptr(), max(G.stride(0), n), dE.data_ptr() if want_e else None, N,
+                                      db.data_ptr() if want_e else None, dW.data_ptr() if want_w else None, n, N, K, n,
+                                      float(p), seed.data_ptr() if seed is not None else None, 0, ws.data_ptr(), ws.numel(),
+                                      _stream_ptr(E.device)))
+    return dE, db, dW
+
+
+class _EmbedXW(torch.autograd.Function):
+    """Saves the three parameters and the seed; the activation is recomputed where it is needed."""
+
+    @staticmethod
+    def forward(ctx, E: Tensor, b: Tensor, W: Tensor, p: float, seed: Optional[Tensor]):
+        ctx.p = p
+        ctx.has_seed = seed is not None
+        ctx.save_for_backward(E, b, W, *([seed] if seed is not None else []))
+        return embed_xw_forward(E.detach(), b.detach(), W.detach(), p, seed)
+
+    @staticmethod
+    def backward(ctx, G: Tensor):
+        E, b, W = ctx.saved_tensors[:3]
+        seed = ctx.saved_tensors[3] if ctx.has_seed else None
+        need = ctx.needs_input_grad
+        dE, db, dW = embed_xw_backward(E, b, W, G, ctx.p, seed, want_e=need[0] or need[1], want_w=need[2])
+        return (dE if need[0] else None), (db if need[1] else None), dW, None, None
+
+
+def embed_xw(E: Tensor, b: Tensor, W: Tensor, p: float = 0.0, seed: Optional[Tensor] = None) -> Tensor:
+    """dropout(selu(E.t() + b), p) @ W with gradients for E [K, N], b [K] and W [K, n].  p > 0 is training-mode inverted
+    dropout whose mask is a stateless hash of (seed, node, column) -- the library's random stream, not torch's; `seed`
+    None draws one from torch's generator on the device (`dense.new_seed`)."""
+    _require(E, b, W)
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"embed_xw: dropout rate {p} outside [0, 1)")
+    if p == 0.0:
+        seed = None
+    elif seed is None:
+        seed = new_seed(E.device)
+    return _EmbedXW.apply(E, b, W, p, seed)

@@ -1,4 +1,4 @@
-"""GCN: drop-in for `textgcn.lib.models.GCN` (textgcn/lib/models.py:6-25).
+"""GCN and EGCN: drop-ins for `textgcn.lib.models.GCN` (textgcn/lib/models.py:6-25) and `.EGCN` (:28-52).
 
 Same constructor signature and defaults, same `layers` ModuleList (state_dict keys
 `layers.{i}.weight` (in, out) / `layers.{i}.bias`), same forward: dropout between layers, none
@@ -16,8 +16,9 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from . import dense
-from .conv import GCNConv, propagate
+from . import dense, embed
+from .conv import GCNConv, features_times, is_sparse_identity, propagate
+from .plan import _require_cuda
 
 # Opt-in: the reference network has no non-linearity (models.py:22 is commented out) and dropout is the
 # identity in eval mode, so without autograd the L-layer forward
@@ -101,4 +102,86 @@ class GCN(nn.Module):
                     pending = float(self.dropout)
                 else:
                     x = nn.functional.dropout(x, p=self.dropout, training=self.training)
+        return x
+
+
+# On by default: EGCN's front end on exact-identity features -- Linear, SELU, dropout and the first layer's x @ W -- as ONE
+# product that never stores the N x embedding_dim activation (pytextgcn_amd/embed.py).  Off: the same arithmetic composed
+# from the package's other kernels and torch's SELU / dropout, for A/B runs and tests.
+_FUSED_EMBEDDING = True
+
+
+def enable_fused_embedding(on: bool = True) -> bool:
+    """Returns the previous setting."""
+    global _FUSED_EMBEDDING
+    was, _FUSED_EMBEDDING = _FUSED_EMBEDDING, bool(on)
+    return was
+
+
+class EmbeddingLinear(nn.Linear):
+    """`layers[0]` of EGCN: torch's `nn.Linear` (same parameters, same init, same state_dict keys) whose forward runs on
+    this package's kernels for every feature format of text2graph.py:226-246 -- `features_times` on `weight.t()`, plus
+    bias; no torch.sparse.mm, no vendor GEMM, no CPU fallback."""
+
+    def forward(self, x):
+        _require_cuda(x, "x")
+        y = features_times(x, self.weight.t(), self.in_features)
+        return y if self.bias is None else y + self.bias
+
+
+class EGCN(nn.Module):
+    """Drop-in for `textgcn.lib.models.EGCN` (textgcn/lib/models.py:28-52): an embedding `Linear(in_channels,
+    embedding_dim)`, SELU, dropout, then GCNConv layers (embedding_dim -> h, (h -> h) x (n_gcn - 2), h -> out).
+
+    Same constructor signature and defaults, same `layers` ModuleList (`layers.0.weight` is the Linear's
+    (embedding_dim, in_channels), the GCNConv keys keep PyG's (in, out) layout).  As in the reference `self.activation` is
+    constructed and never applied (models.py:32,49), and the dropout ALSO FOLLOWS THE LAST LAYER: the reference's guard
+    `i < len(self.layers) - 1` is evaluated while enumerating `self.layers[1:]` (models.py:46-50), so it always holds and in
+    training mode the logits themselves are dropped.  Both facts are kept.  Eval mode has no dropout anywhere.
+
+    Exact-identity features take the fused product of `pytextgcn_amd.embed` -- by default in eval mode and whenever
+    `dropout` is 0; in training with 0 < dropout < 1 only while `enable_fused_dropout()` is on, because the mask is then
+    drawn from the library's random stream, not torch's (the rule `GCN` follows).  Everything else, and everything after
+    `enable_fused_embedding(False)`, is composed from `EmbeddingLinear`, torch's SELU and dropout, and `GCNConv`."""
+
+    def __init__(self, in_channels, out_channels, embedding_dim=2000, n_gcn=2, n_hidden_gcn=64, activation=nn.ReLU,
+                 dropout=0.5):
+        super().__init__()
+        self.activation = activation()
+        self.dropout = dropout
+        self.layers = nn.ModuleList([EmbeddingLinear(in_channels, embedding_dim),
+                                     GCNConv(embedding_dim, n_hidden_gcn, add_self_loops=True)])
+        for _ in range(n_gcn - 2):
+            self.layers.append(GCNConv(n_hidden_gcn, n_hidden_gcn, add_self_loops=True))
+        self.layers.append(GCNConv(n_hidden_gcn, out_channels, add_self_loops=True))
+
+    def _dropout(self, x):
+        return nn.functional.dropout(x, p=self.dropout, training=True) if self.training else x
+
+    def takes_fused_path(self, x) -> bool:
+        """Whether `forward` on the features `x` runs the fused embedding product (see the class docstring)."""
+        p = float(self.dropout)
+        if not (_FUSED_EMBEDDING and x.is_sparse and x.size(1) == self.layers[0].in_features):
+            return False
+        if self.training and p != 0.0 and not (_FUSED_DROPOUT and 0.0 < p < 1.0):
+            return False
+        return is_sparse_identity(x)
+
+    def forward(self, g):
+        x = g.x
+        emb, first = self.layers[0], self.layers[1]
+        if self.takes_fused_path(x):
+            _require_cuda(x, "g.x")
+            plan = first.plan(x, g.edge_index, g.edge_attr)
+            xw = embed.embed_xw(emb.weight, emb.bias, first.weight, float(self.dropout) if self.training else 0.0)
+            x = propagate(plan, xw, first.bias)
+        else:
+            x = emb(x)
+            x = torch.selu(x)
+            x = self._dropout(x)
+            x = first(x, g.edge_index, g.edge_attr)
+        x = self._dropout(x)
+        for layer in self.layers[2:]:
+            x = layer(x, g.edge_index, g.edge_attr)
+            x = self._dropout(x)                 # also after the last layer, as the reference does
         return x
