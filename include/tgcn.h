@@ -420,7 +420,55 @@ int tgcn_embed_xw_grad(const float *E, int64_t lde, const float *b, const float 
                        tgcn_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Word-word PMI edges (graph construction).  Replaces the reference's Cython
+ * JumpingKnowledge(mode="lstm") of the reference's JumpingKnowledgeNetwork (textgcn/lib/models.py:64,75; PyG 1.6.3): a
+ * bidirectional LSTM of hidden width H over the L per-layer activations x_t [N, C] of every node, a Linear(2 H -> 1) on
+ * [h_fwd_t | h_bwd_t], a softmax over the layers and the weighted sum
+ *       alpha[i, :] = softmax_t(att_w . [h_fwd_t(i) | h_bwd_t(i)] + att_b),      out[i, :] = sum_t alpha[i, t] x_t[i, :].
+ * The L inputs are L separate matrices: `xs` and `ldxs` are HOST arrays of L device pointers / leading dimensions (read
+ * during the call), 1 <= L <= TGCN_JK_MAX_LAYERS; no alignment or padding is asked of them.  `lstm` is a HOST array of the
+ * 8 device pointers {weight_ih [4 H, C] stride ldwi, weight_hh [4 H, H] stride ldwh, bias_ih [4 H], bias_hh [4 H]} of the
+ * forward direction followed by the same four of the reverse direction, torch's nn.LSTM layout and gate order i, f, g, o.
+ * att_w [2 H], att_b [1].  relu != 0: out = max(out, 0).  C, H >= 1, N >= 0; all offsets are 64-bit; no atomics.
+ *
+ *   tgcn_jk_lstm_forward   the whole step as one kernel on v_mfma_f32_32x32x2_f32: writes out [N, C] and alpha [N, L] and
+ *                          nothing else -- no gate, cell or hidden value reaches memory.  H <= 256
+ *                          (tgcn_jk_lstm_forward_supported(H) != 0); a wider one is TGCN_E_INVALID.
+ *
+ * The same arithmetic in pieces, for the backward by recomputation over row chunks and for the composed forward (R = rows of
+ * the chunk; the products x_t W_ih^T, h W_hh^T, d gates W_hh, d gates W_ih and the weight gradients are tgcn_gemm_nt / _nn /
+ * _tn, the bias gradients tgcn_colsum):
+ *   tgcn_jk_cell            gates [R, 4 H] <- (sigmoid, sigmoid, tanh, sigmoid)(pre_x + pre_h + b_ih + b_hh), c = f c_prev + i g,
+ *                           h = o tanh(c).  pre_h = NULL / c_prev = NULL: the first step (h = c = 0).  gates may be pre_x.
+ *   tgcn_jk_attention       alpha and out from stored hidden states: h_fwd / h_bwd + t * hstep is h_t [R, H] stride ldh.
+ *   tgcn_jk_attention_grad  dscore [R, L]: d score_t = alpha_t (d alpha_t - sum_s alpha_s d alpha_s), d alpha_t = G' . x_t,
+ *                           G' = G where out > 0 (out != NULL: the relu epilogue) or G.
+ *   tgcn_jk_cell_grad       d gates_t [R, 4 H] (at the pre-activations) from d h_t = dh_rec (NULL: none) + dscore_t att_w_dir
+ *                           (dscore_t: column t of dscore, stride ldds; att_w_dir: the direction's H entries of att_w) and
+ *                           dc = d c_t (dc_zero != 0: none yet); dc leaves as d c_{t-1}.
+ *   tgcn_jk_input_grad      d x_t [R, C] = alpha_t G' + T    (alpha_t: column t of alpha, stride lda; T = d gates_t @ W_ih).
+ */
+#define TGCN_JK_MAX_LAYERS 8
+int tgcn_jk_lstm_forward_supported(int H);
+int tgcn_jk_lstm_forward(const float *const *xs, const int64_t *ldxs, int L, int64_t N, int C, int H,
+                         const float *const *lstm, int64_t ldwi, int64_t ldwh, const float *att_w, const float *att_b,
+                         float *out, int64_t ldo, float *alpha, int64_t lda, int relu, tgcn_stream stream);
+int tgcn_jk_cell(const float *pre_x, int64_t ldpx, const float *pre_h, int64_t ldph, const float *b_ih, const float *b_hh,
+                 const float *c_prev, int64_t ldcp, float *gates, int64_t ldg, float *c, int64_t ldc, float *h, int64_t ldh,
+                 int64_t R, int H, tgcn_stream stream);
+int tgcn_jk_attention(const float *const *xs, const int64_t *ldxs, int L, int64_t R, int C, int H, const float *h_fwd,
+                      const float *h_bwd, int64_t ldh, int64_t hstep, const float *att_w, const float *att_b, float *out,
+                      int64_t ldo, float *alpha, int64_t lda, int relu, tgcn_stream stream);
+int tgcn_jk_attention_grad(const float *const *xs, const int64_t *ldxs, int L, int64_t R, int C, const float *G, int64_t ldg,
+                           const float *out, int64_t ldo, const float *alpha, int64_t lda, float *dscore, int64_t ldds,
+                           tgcn_stream stream);
+int tgcn_jk_cell_grad(const float *gates, int64_t ldg, const float *c, int64_t ldc, const float *c_prev, int64_t ldcp,
+                      const float *dh_rec, int64_t lddh, const float *dscore_t, int64_t ldds, const float *att_w_dir, float *dc,
+                      int64_t lddc, int dc_zero, float *dgates, int64_t lddg, int64_t R, int H, tgcn_stream stream);
+int tgcn_jk_input_grad(float *dx, int64_t lddx, const float *T, int64_t ldt, const float *G, int64_t ldg, const float *out,
+                       int64_t ldo, const float *alpha_t, int64_t lda, int64_t R, int C, tgcn_stream stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Word-word PMI edges (graph construction). Replaces the reference's Cython
  * entry point `compute_word_word_edges(X, n_vocab, n_documents, seq_len, window_size, n_jobs, verbose)`
  * (textgcn/lib/clib/graphbuilder.pyx:23-25, called at text2graph.py:156-160) and its test hook
  * `sliding_window_tester` (:263-275).  Results are bit-identical to the reference: same uint32

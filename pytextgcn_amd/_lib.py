@@ -103,6 +103,19 @@ SIGNATURES = {
     "tgcn_embed_xw_grad": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                                    c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_double, c_void_p, c_int64,
                                    c_void_p, c_size_t, c_void_p]),
+    "tgcn_jk_lstm_forward_supported": (c_int, [c_int]),
+    "tgcn_jk_lstm_forward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_int64, c_int64, c_void_p,
+                                     c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p]),
+    "tgcn_jk_cell": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                             c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p]),
+    "tgcn_jk_attention": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64, c_int64,
+                                  c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p]),
+    "tgcn_jk_attention_grad": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64,
+                                       c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "tgcn_jk_cell_grad": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                  c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p]),
+    "tgcn_jk_input_grad": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                   c_int64, c_int64, c_int, c_void_p]),
     "tgcn_wwedges_create": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p,
                                     POINTER(c_void_p)]),
     "tgcn_wwedges_query": (c_int, [c_void_p, c_int, POINTER(c_int64)]),

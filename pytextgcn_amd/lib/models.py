@@ -1,6 +1,5 @@
 """`textgcn.lib.models` import path (flat_amazon.py:14 `from textgcn.lib.models import *`;
-perlevel_amazon.py:14 `from textgcn.lib.models import JumpingKnowledgeNetwork, GCN, EGCN` -- the JumpingKnowledgeNetwork
-is not part of this package)."""
-from ..models import EGCN, GCN
+perlevel_amazon.py:14 `from textgcn.lib.models import JumpingKnowledgeNetwork, GCN, EGCN`)."""
+from ..models import EGCN, GCN, JumpingKnowledgeNetwork
 
-__all__ = ["GCN", "EGCN"]
+__all__ = ["GCN", "EGCN", "JumpingKnowledgeNetwork"]

@@ -1,4 +1,5 @@
-"""GCN and EGCN: drop-ins for `textgcn.lib.models.GCN` (textgcn/lib/models.py:6-25) and `.EGCN` (:28-52).
+"""GCN, EGCN and JumpingKnowledgeNetwork: drop-ins for `textgcn.lib.models.GCN` (textgcn/lib/models.py:6-25), `.EGCN`
+(:28-52) and `.JumpingKnowledgeNetwork` (:55-81; its docstring below).  For GCN and EGCN:
 
 Same constructor signature and defaults, same `layers` ModuleList (state_dict keys
 `layers.{i}.weight` (in, out) / `layers.{i}.bias`), same forward: dropout between layers, none
@@ -18,6 +19,7 @@ from torch import nn
 
 from . import dense, embed
 from .conv import GCNConv, features_times, is_sparse_identity, propagate
+from .jk import JumpingKnowledge
 from .plan import _require_cuda
 
 # Opt-in: the reference network has no non-linearity (models.py:22 is commented out) and dropout is the
@@ -185,3 +187,44 @@ class EGCN(nn.Module):
             x = layer(x, g.edge_index, g.edge_attr)
             x = self._dropout(x)                 # also after the last layer, as the reference does
         return x
+
+
+class JumpingKnowledgeNetwork(nn.Module):
+    """Drop-in for `textgcn.lib.models.JumpingKnowledgeNetwork` (textgcn/lib/models.py:55-81): `n_gcn` GCNConv layers
+    (in -> h, (h -> h) x (n_gcn - 2), h -> h), `jk = JumpingKnowledge("lstm", channels=h, num_layers=n_gcn)` over their
+    outputs, then `lin = Linear(h, out)`.
+
+    Same constructor signature and defaults, same state_dict keys (`layers.{i}.*`, `jk.lstm.*`, `jk.att.*`, `lin.*`: a
+    checkpoint of the reference loads with strict=True), same forward: EVERY layer is followed by dropout and the dropped
+    tensor is what the aggregation sees; then `jk`, the activation -- which, unlike in `GCN` and `EGCN`, IS applied here
+    (models.py:76) -- dropout, and `lin`.  `nn.ReLU` runs in the epilogue of the aggregation kernel
+    (pytextgcn_amd/jk.py); any other module is called on its result.  `lin` runs on this package's kernels
+    (`EmbeddingLinear`): no vendor GEMM, no CPU fallback.
+
+    Dropout is torch's `F.dropout` throughout, drawing from torch's random stream: `enable_fused_dropout` does not apply
+    to this model.  At most 8 layers (`jk.MAX_LAYERS`)."""
+
+    def __init__(self, in_channels, out_channels, n_gcn=2, n_hidden_gcn=64, activation=nn.ReLU, dropout=0.5):
+        super().__init__()
+        self.activation = activation()
+        self.dropout = dropout
+        self.layers = nn.ModuleList([GCNConv(in_channels, n_hidden_gcn, add_self_loops=True)])
+        for _ in range(n_gcn - 2):
+            self.layers.append(GCNConv(n_hidden_gcn, n_hidden_gcn, add_self_loops=True))
+        self.layers.append(GCNConv(n_hidden_gcn, n_hidden_gcn, add_self_loops=True))
+        self.jk = JumpingKnowledge(mode="lstm", channels=n_hidden_gcn, num_layers=n_gcn)
+        self.lin = EmbeddingLinear(n_hidden_gcn, out_channels)
+
+    def forward(self, g):
+        x = g.x
+        acts = []
+        for layer in self.layers:
+            x = layer(x, g.edge_index, g.edge_attr)
+            x = nn.functional.dropout(x, p=self.dropout, training=self.training)
+            acts += [x]
+        relu = type(self.activation) is nn.ReLU
+        x = self.jk.aggregate(acts, relu=relu)
+        if not relu:
+            x = self.activation(x)
+        x = nn.functional.dropout(x, p=self.dropout, training=self.training)
+        return self.lin(x)
