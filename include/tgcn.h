@@ -420,6 +420,38 @@ int tgcn_embed_xw_grad(const float *E, int64_t lde, const float *b, const float 
                        tgcn_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The middle of the reference's MLP (textgcn/lib/models.py:83-102: `x = dropout(selu(Linear(x)))` feeding the next
+ * Linear), as ONE product per layer.  Z [N, k] (row-major, leading dimension ldz >= k) is a layer's stored
+ * pre-activation WITHOUT its bias b [k]; W [n, k] (leading dimension ldw >= k) is the next nn.Linear's weight in torch's
+ * own [out, in] layout and c [n] its bias (NULL: none).  With
+ *       a(i, j) = s * keep(i, j) * selu(Z[i, j] + b[j]),      s = 1 / (1 - p),
+ * keep(i, j) the decision of tgcn_gemm_*_dropout for mask row mask_row0 + i and column j (same hash, same threshold
+ * clamp, same one-element int64 device seed), and selu with torch's constants:
+ *   tgcn_mlp_act_linear        C[i, 0:n]  = sum_j a(i, j) W[0:n, j] (+ c[0:n])               C [N, n] stride ldc
+ *   tgcn_mlp_act_linear_grad   dZ[i, j]   = s keep(i, j) selu'(Z[i, j] + b[j]) sum_m G[i, m] W[m, j]    (Z's layout, stride lddz)
+ *                              db[j]      = sum_i dZ[i, j]
+ *                              dW[m, j]   = sum_i G[i, m] a(i, j)      (W's layout, stride lddw)   G = dC [N, n] stride ldg
+ * The N x k activation is never stored: a is formed in registers on its way into the fp32 matrix cores, and recomputed
+ * (same mask) for dW.  p = 0 or seed = NULL: no mask, s = 1.  0 <= p < 1.  N >= 0, k >= 1, n >= 1 (wider operands run as
+ * column groups of 256 and chunks of k inside the call); all offsets are 64-bit.  Z, G, C, dZ, W and dW are taken with ANY
+ * leading dimension >= their width and any 4-byte alignment: every load and store of these kernels is a dword, so there is
+ * no vector path with % 4 or 16-byte conditions and hence one result whatever the strides are (db's column sums take
+ * tgcn_colsum's float4 loads where dZ allows them).  The mask row offset is an argument; no thread-local state is read.
+ * tgcn_mlp_act_linear_grad: dZ and db are computed together (both or neither), dW on its own.  The workspace
+ * (tgcn_mlp_act_linear_grad_workspace_bytes; needed whenever N > 0) holds partial sums of db and dW, nothing of size N x k.
+ * Fixed summation orders, no atomics: reproducible run to run.  The calls only enqueue on `stream`.  NULL operands, p
+ * outside [0, 1), mask_row0 < 0, a leading dimension below the width and a short workspace are TGCN_E_INVALID before
+ * anything is enqueued. */
+int tgcn_mlp_act_linear(const float *Z, int64_t ldz, const float *b, const float *W, int64_t ldw, const float *c, float *C,
+                        int64_t ldc, int64_t N, int k, int n, double p, const uint64_t *seed, int64_t mask_row0,
+                        tgcn_stream stream);
+size_t tgcn_mlp_act_linear_grad_workspace_bytes(int64_t N, int k, int n);
+int tgcn_mlp_act_linear_grad(const float *Z, int64_t ldz, const float *b, const float *W, int64_t ldw, const float *G,
+                             int64_t ldg, float *dZ, int64_t lddz, float *db, float *dW, int64_t lddw, int64_t N, int k,
+                             int n, double p, const uint64_t *seed, int64_t mask_row0, void *workspace,
+                             size_t workspace_bytes, tgcn_stream stream);
+
+/* ---------------------------------------------------------------------------------------------
  * JumpingKnowledge(mode="lstm") of the reference's JumpingKnowledgeNetwork (textgcn/lib/models.py:64,75; PyG 1.6.3): a
  * bidirectional LSTM of hidden width H over the L per-layer activations x_t [N, C] of every node, a Linear(2 H -> 1) on
  * [h_fwd_t | h_bwd_t], a softmax over the layers and the weighted sum

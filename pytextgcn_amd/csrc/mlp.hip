@@ -1,0 +1,500 @@
+// The middle of the reference's MLP (textgcn/lib/models.py:83-102): x = dropout(selu(Linear(x))) feeding the next Linear.
+// Z [N, k] is a layer's stored pre-activation WITHOUT its bias b [k]; W [n, k] is the next nn.Linear's weight in torch's
+// [out, in] layout, c [n] its bias.  Element a(i, j) = s * keep(i, j) * selu(Z[i, j] + b[j]) is formed in registers on its
+// way into the matrix cores and never stored:
+//     tgcn_mlp_act_linear        C[i, m]  = sum_j a(i, j) W[m, j] (+ c[m])
+//     tgcn_mlp_act_linear_grad   dZ[i, j] = s keep(i, j) selu'(Z[i, j] + b[j]) sum_m G[i, m] W[m, j],   db[j] = sum_i dZ[i, j],
+//                                dW[m, j] = sum_i G[i, m] a(i, j)                       (a recomputed, the same mask)
+// keep(i, j) is the decision of tgcn_gemm_*_dropout (drop_hash.h) for mask row mask_row0 + i, column j.
+//
+// All three products run on v_mfma_f32_32x32x2_f32 (exact fp32; fragment maps as in dense.hip / embed.hip: lane l feeds
+// A[l & 31][l >> 5] and B[l >> 5][l & 31], register r of lane l is C[(r & 3) + 8 (r >> 2) + 4 (l >> 5)][l & 31]).  Z, W and
+// G are row-major, so every global load here has the lanes of a half wave on 32 consecutive floats of one row (one
+// 128-byte run); they are plain dword loads, which ask nothing of the strides or the alignment.  Where the matrix cores
+// want an operand with the ROW on the lane (the forward's activation and weight tiles, dZ's tile of G), the tile goes
+// through LDS with an odd row stride.
+#include <algorithm>
+
+#include "common.h"
+#include "drop_hash.h"
+
+namespace tgcn {
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// torch's constants (aten/src/ATen/native/Activation.cpp: selu), as embed.hip has them
+constexpr float kSeluScale = 1.0507009873554805f;
+constexpr float kSeluNeg = static_cast<float>(1.0507009873554805 * 1.6732632423543772);   // scale * alpha
+
+struct MlpDrop {
+    const uint64_t *seed;  // device pointer (read by the kernels: safe under HIP-graph capture)
+    uint32_t thresh;       // keep iff hash >= thresh
+    float scale;           // 1 / (1 - p)
+    int64_t row0;          // row i is mask row i + row0
+};
+
+__device__ __forceinline__ float selu_f(float x) { return x > 0.f ? kSeluScale * x : kSeluNeg * expm1f(x); }
+__device__ __forceinline__ float selu_grad_f(float x) { return x > 0.f ? kSeluScale : kSeluNeg * expf(x); }
+
+// a(i, j) from z = Z[i, j] + b[j]; `key` is row i's key, `col_term` column j's term of the hash
+template <bool DROP>
+__device__ __forceinline__ float mlp_act(float z, uint32_t key, uint32_t col_term, const MlpDrop &d) {
+    const float a = selu_f(z);
+    if constexpr (DROP) return drop_hash_keep(key, col_term, d.thresh) ? a * d.scale : 0.f;
+    return a;
+}
+
+template <bool DROP>
+__device__ __forceinline__ uint32_t mlp_row_key(const MlpDrop &d, int64_t i) {
+    if constexpr (DROP) {
+        const uint64_t seed = *d.seed;
+        return drop_row_key(static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), i + d.row0);
+    }
+    return 0u;
+}
+
+__device__ __forceinline__ int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+
+// ---------------------------------------------------------------------------------------------
+// Forward.  A workgroup owns 128 rows, a wave 32 of them and all 32 NT result columns.  Per chunk of 32 reduction
+// indices the workgroup stages its 128 x 32 tile of Z and the NT 32 x 32 tiles of W in LDS, both as [row][33]: the
+// staging writes (lanes along a row) and the operand reads (lanes down a column, 33 floats apart) are conflict-free.
+// Per MFMA step a lane forms ONE element a(i, j) -- its row i is fixed, so the row key of the hash is paid once per
+// lane -- and spends it on NT tiles.
+// ---------------------------------------------------------------------------------------------
+template <int NT, bool DROP>
+__global__ __launch_bounds__(256, 2) void k_mlp_fwd(const float *__restrict__ Z, int64_t ldz, const float *__restrict__ b,
+                                                    const float *__restrict__ W, int64_t ldw, const float *__restrict__ cb,
+                                                    float *__restrict__ C, int64_t ldc, int64_t N, int K, int n,
+                                                    const MlpDrop d) {
+    constexpr int KC = 32, NP = 32 * NT, LD = KC + 1;
+    __shared__ float Ws[NP * LD];
+    __shared__ float Zs[128 * LD];
+    __shared__ float bs[KC];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, c = lane & 31;
+    const int64_t blk0 = int64_t(blockIdx.x) * 128;
+    const int64_t row0 = blk0 + wave * 32;
+    const int64_t i = row0 + c;
+    const bool live = i < N;
+    const uint32_t key = mlp_row_key<DROP>(d, i);
+    const int skk = tid & 31, sr = tid >> 5;               // staging: this thread's column of the chunk and its first row
+    f32x16 acc[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+
+    for (int k0 = 0; k0 < K; k0 += KC) {
+        const bool kin = k0 + skk < K;
+        __syncthreads();                                   // the previous chunk has been read
+#pragma unroll 4
+        for (int u = 0; u < 4 * NT; ++u) {
+            const int m = sr + 8 * u;
+            Ws[m * LD + skk] = (kin && m < n) ? W[int64_t(m) * ldw + k0 + skk] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            const int r = sr + 8 * u;
+            Zs[r * LD + skk] = (kin && blk0 + r < N) ? Z[(blk0 + r) * ldz + k0 + skk] : 0.f;
+        }
+        if (tid < KC) bs[tid] = kin ? b[k0 + tid] : 0.f;
+        __syncthreads();
+        const float *zr = Zs + (wave * 32 + c) * LD;
+#pragma unroll
+        for (int s = 0; s < KC / 2; ++s) {
+            const int kk = 2 * s + half, k = k0 + kk;
+            const float a = (live && k < K) ? mlp_act<DROP>(zr[kk] + bs[kk], key, drop_col_term(k), d) : 0.f;
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, Ws[(32 * t + c) * LD + kk], acc[t], 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const int col = 32 * t + c;
+        const float bias = (cb != nullptr && col < n) ? cb[col] : 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int64_t row = row0 + acc_row(r, half);
+            if (row < N && col < n) C[row * ldc + col] = acc[t][r] + bias;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// dZ, in Z's layout: T[i, j] = sum_m G[i, m] W[m, j].  A wave keeps its 32 rows of G in registers (the A operand, the row
+// on the lane: read once with the lanes along a row, turned through the wave's own [32][33] tile in LDS, then reused over
+// all K / 32 tiles of j); the workgroup shares the NT x 32 rows of W for the tile in LDS as they lie in
+// memory (the B operand has the lanes along a row: no transpose, no conflict).  A lane's 16 results are 16 rows of one
+// column, so it pays 16 row keys, once, before the loop over the tiles.  `accum`: the reduction over m is longer than one
+// launch covers (n > 128: more rows of G than a lane has registers for beside the keys) and this is not its first piece:
+// the masked, scaled partial sum is added to what dZ holds.
+// ---------------------------------------------------------------------------------------------
+template <int NT, bool DROP>
+__global__ __launch_bounds__(256, 2) void k_mlp_grad_z(const float *__restrict__ Z, int64_t ldz, const float *__restrict__ b,
+                                                       const float *__restrict__ W, int64_t ldw,
+                                                       const float *__restrict__ G, int64_t ldg, float *__restrict__ dZ,
+                                                       int64_t lddz, int64_t N, int K, int n, int accum, const MlpDrop d) {
+    constexpr int NP = 32 * NT;
+    __shared__ float Ws[NP * 32];
+    __shared__ float Gs[4 * 32 * 33];
+    __shared__ float bs[32];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, c = lane & 31;
+    const int64_t row0 = (int64_t(blockIdx.x) * 4 + wave) * 32;
+    const int sj = tid & 31, sr = tid >> 5;
+    float *gw = Gs + wave * (32 * 33);                     // this wave's 32 x 32 tile of G, [row][33]
+    float g[16 * NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const int m = 32 * t + c;
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {                     // lanes along a row of G: 128 bytes per half wave
+            const int r = 2 * u + half;
+            gw[r * 33 + c] = (row0 + r < N && m < n) ? G[(row0 + r) * ldg + m] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < 16; ++s) g[16 * t + s] = gw[c * 33 + 2 * s + half];   // lane c takes row c, column 2 s + half
+        __syncthreads();
+    }
+    uint32_t keys[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) keys[r] = mlp_row_key<DROP>(d, row0 + acc_row(r, half));
+
+    for (int j0 = 0; j0 < K; j0 += 32) {
+        __syncthreads();                                   // the previous tile has been read
+#pragma unroll 4
+        for (int u = 0; u < 4 * NT; ++u) {
+            const int m = sr + 8 * u;
+            Ws[m * 32 + sj] = (j0 + sj < K && m < n) ? W[int64_t(m) * ldw + j0 + sj] : 0.f;
+        }
+        if (tid < 32) bs[tid] = j0 + tid < K ? b[j0 + tid] : 0.f;
+        const int j = j0 + c;
+        float z[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int64_t row = row0 + acc_row(r, half);
+            z[r] = (row < N && j < K) ? Z[row * ldz + j] : 0.f;
+        }
+        __syncthreads();
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+        for (int s = 0; s < 16 * NT; ++s)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(g[s], Ws[(2 * s + half) * 32 + c], acc, 0, 0, 0);
+        const float bj = bs[c];
+        const uint32_t col_term = drop_col_term(j);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int64_t row = row0 + acc_row(r, half);
+            if (row < N && j < K) {
+                float v = acc[r] * selu_grad_f(z[r] + bj);
+                if constexpr (DROP) v = drop_hash_keep(keys[r], col_term, d.thresh) ? v * d.scale : 0.f;
+                float *out = dZ + row * lddz + j;
+                *out = accum ? *out + v : v;
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// dW[m, j] = sum_i G[i, m] a(i, j), in W's layout: the reduction runs over the rows, and both operands have the lanes
+// along a row as they lie in memory.  blockIdx.x is a tile of 32 columns j, blockIdx.y a slice of the rows.  The workgroup
+// reads 128 rows x 32 columns of Z, forms a(i, j) ONCE per element and leaves it in LDS (the row keys of the tile are
+// computed once, by 128 threads, and shared through LDS); the 4 waves split the rows m of dW (TW tiles of 32 each) and
+// read their slab of G straight from memory, 128 bytes per half wave.  The slices' partial sums go to the workspace and
+// are added in a fixed order by k_mlp_reduce_w.
+// ---------------------------------------------------------------------------------------------
+constexpr int kWChunk = 128;   // rows per staged tile
+
+template <int TW, bool DROP>
+__global__ __launch_bounds__(256, 2) void k_mlp_grad_w(const float *__restrict__ Z, int64_t ldz, const float *__restrict__ b,
+                                                       const float *__restrict__ G, int64_t ldg, float *__restrict__ part,
+                                                       int64_t N, int K, int n, int64_t chunks_per_slice, const MlpDrop d) {
+    constexpr int NP = 128 * TW;
+    __shared__ float As[kWChunk * 32];
+    __shared__ uint32_t ks[kWChunk];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, c = lane & 31;
+    const int j0 = blockIdx.x * 32;
+    const int kpad = gridDim.x * 32;
+    const int64_t i_begin = int64_t(blockIdx.y) * chunks_per_slice * kWChunk;
+    const int64_t i_stop = i_begin + chunks_per_slice * kWChunk;
+    const int64_t i_end = i_stop < N ? i_stop : N;
+    const bool computes = wave * TW * 32 < n;             // a wave whose rows of dW are all padding only helps staging
+    const int sj = tid & 31, sr = tid >> 5;                // staging: this thread's column of the tile and its first row
+    const int j = j0 + sj;
+    const float bj = j < K ? b[j] : 0.f;
+    const uint32_t col_term = drop_col_term(j);
+    f32x16 acc[TW];
+#pragma unroll
+    for (int t = 0; t < TW; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+
+    for (int64_t i0 = i_begin; i0 < i_end; i0 += kWChunk) {
+        float z[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            const int64_t i = i0 + sr + 8 * u;
+            z[u] = (i < i_end && j < K) ? Z[i * ldz + j] : 0.f;
+        }
+        __syncthreads();                                   // the previous tile has been read
+        if constexpr (DROP) {
+            if (tid < kWChunk) ks[tid] = mlp_row_key<DROP>(d, i0 + tid);
+            __syncthreads();
+        }
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            const int r = sr + 8 * u;
+            const int64_t i = i0 + r;
+            const uint32_t key = DROP ? ks[r] : 0u;
+            As[r * 32 + sj] = (i < i_end && j < K) ? mlp_act<DROP>(z[u] + bj, key, col_term, d) : 0.f;
+        }
+        __syncthreads();
+        if (computes) {
+#pragma unroll 8
+            for (int s = 0; s < kWChunk / 2; ++s) {
+                const int ii = 2 * s + half;
+                const int64_t i = i0 + ii;
+                const float a = As[ii * 32 + c];
+#pragma unroll
+                for (int t = 0; t < TW; ++t) {
+                    const int m = (wave * TW + t) * 32 + c;
+                    const float gv = (i < i_end && m < n) ? G[i * ldg + m] : 0.f;
+                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(gv, a, acc[t], 0, 0, 0);
+                }
+            }
+        }
+    }
+    float *out = part + int64_t(blockIdx.y) * NP * kpad + j0 + c;
+#pragma unroll
+    for (int t = 0; t < TW; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) out[int64_t((wave * TW + t) * 32 + acc_row(r, half)) * kpad] = acc[t][r];
+}
+
+__global__ __launch_bounds__(256) void k_mlp_reduce_w(const float *__restrict__ part, int slices, int np, int kpad, int n,
+                                                      int K, float *__restrict__ dW, int64_t lddw) {
+    const int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (e >= int64_t(n) * K) return;
+    const int m = static_cast<int>(e / K), j = static_cast<int>(e % K);
+    const float *p = part + int64_t(m) * kpad + j;
+    const int64_t stride = int64_t(np) * kpad;
+    float s = 0.f;
+    for (int q = 0; q < slices; ++q) s += p[q * stride];
+    dW[int64_t(m) * lddw + j] = s;
+}
+
+constexpr int kFwdGroup = 256;   // result columns of one forward launch (8 tiles)
+constexpr int kGzGroup = 128;    // reduction length of one dZ launch (4 tiles: 64 registers of G per lane)
+constexpr int kWGroup = 256;     // rows of dW of one dW launch (4 waves x 2 tiles)
+
+// how the rows are cut into slices for dW: about 512 workgroups in all, at most 256 slices
+void grad_w_split(int64_t N, int K, int64_t &slices, int64_t &chunks_per_slice) {
+    const int64_t chunks = std::max<int64_t>(1, (N + kWChunk - 1) / kWChunk);
+    const int64_t ktiles = (int64_t(K) + 31) / 32;
+    const int64_t want = std::min<int64_t>(256, std::max<int64_t>(1, 512 / ktiles));
+    chunks_per_slice = (chunks + want - 1) / want;
+    slices = (chunks + chunks_per_slice - 1) / chunks_per_slice;
+}
+
+// the workspace: the column-sum partials of db first, the slices' partial sums of dW after them
+size_t db_floats(int64_t N, int K) { return static_cast<size_t>(colsum_blocks(N)) * static_cast<size_t>(K); }
+
+size_t dw_floats(int64_t N, int K, int n) {
+    int64_t slices, cps;
+    grad_w_split(N, K, slices, cps);
+    const int64_t kpad = (int64_t(K) + 31) / 32 * 32;
+    const int64_t np = std::min(n, kWGroup) > 128 ? 256 : 128;
+    return static_cast<size_t>(slices * np * kpad);
+}
+
+int make_mlp_drop(const char *fn, double p, const uint64_t *seed, int64_t mask_row0, MlpDrop &d, bool &on) {
+    if (!(p >= 0.0 && p < 1.0)) {
+        set_error("%s: p must be in [0, 1) (p=%g)", fn, p);
+        return TGCN_E_INVALID;
+    }
+    if (mask_row0 < 0) {
+        set_error("%s: mask_row0 must be >= 0 (%lld)", fn, (long long)mask_row0);
+        return TGCN_E_INVALID;
+    }
+    on = p > 0.0 && seed != nullptr;
+    d.seed = seed;
+    d.thresh = on ? drop_threshold(p) : 0u;
+    d.scale = on ? static_cast<float>(1.0 / (1.0 - p)) : 1.f;
+    d.row0 = mask_row0;
+    return TGCN_OK;
+}
+
+int check_sizes(const char *fn, int64_t N, int K, int n) {
+    if (N < 0 || K <= 0 || n <= 0) {
+        set_error("%s: need N >= 0, k >= 1 and n >= 1 (N=%lld, k=%d, n=%d)", fn, (long long)N, K, n);
+        return TGCN_E_INVALID;
+    }
+    return TGCN_OK;
+}
+
+#define TGCN_MLP_LD(name, ld, extent)                                                                       \
+    if ((ld) < (extent)) {                                                                                  \
+        set_error("%s: " name " (%lld) is smaller than the extent %lld", fn, (long long)(ld), (long long)(extent)); \
+        return TGCN_E_INVALID;                                                                              \
+    }
+#define TGCN_MLP_PTR(name, ptr)                              \
+    if (!(ptr)) {                                            \
+        set_error("%s: " name " is NULL", fn);               \
+        return TGCN_E_INVALID;                               \
+    }
+
+template <bool DROP>
+int launch_fwd(const float *Z, int64_t ldz, const float *b, const float *W, int64_t ldw, const float *cb, float *C,
+               int64_t ldc, int64_t N, int K, int n, const MlpDrop &d, hipStream_t s) {
+    const unsigned grid = static_cast<unsigned>((N + 127) / 128);
+    for (int col0 = 0; col0 < n; col0 += kFwdGroup) {
+        const int ng = std::min(n - col0, kFwdGroup), nt = (ng + 31) / 32;
+        const float *cg = cb ? cb + col0 : nullptr;
+#define TGCN_MLP_FWD(NT)                                                                                                \
+    hipLaunchKernelGGL((k_mlp_fwd<NT, DROP>), dim3(grid), dim3(256), 0, s, Z, ldz, b, W + int64_t(col0) * ldw, ldw, cg, \
+                       C + col0, ldc, N, K, ng, d)
+        if (nt <= 1) TGCN_MLP_FWD(1);
+        else if (nt <= 2) TGCN_MLP_FWD(2);
+        else if (nt <= 4) TGCN_MLP_FWD(4);
+        else TGCN_MLP_FWD(8);
+#undef TGCN_MLP_FWD
+    }
+    TGCN_HIP_CHECK(hipGetLastError());
+    return TGCN_OK;
+}
+
+template <bool DROP>
+int launch_grad_z(const float *Z, int64_t ldz, const float *b, const float *W, int64_t ldw, const float *G, int64_t ldg,
+                  float *dZ, int64_t lddz, float *db, int64_t N, int K, int n, const MlpDrop &d, float *part,
+                  hipStream_t s) {
+    const unsigned grid = static_cast<unsigned>((N + 127) / 128);
+    for (int col0 = 0; col0 < n; col0 += kGzGroup) {
+        const int ng = std::min(n - col0, kGzGroup), nt = (ng + 31) / 32, accum = col0 > 0;
+#define TGCN_MLP_GZ(NT)                                                                                                   \
+    hipLaunchKernelGGL((k_mlp_grad_z<NT, DROP>), dim3(grid), dim3(256), 0, s, Z, ldz, b, W + int64_t(col0) * ldw, ldw,    \
+                       G + col0, ldg, dZ, lddz, N, K, ng, accum, d)
+        if (nt <= 1) TGCN_MLP_GZ(1);
+        else if (nt <= 2) TGCN_MLP_GZ(2);
+        else TGCN_MLP_GZ(4);
+#undef TGCN_MLP_GZ
+    }
+    TGCN_HIP_CHECK(hipGetLastError());
+    // db[j] = sum_i dZ[i, j]: tgcn_colsum's two passes (colsum.hip), a fixed summation order
+    return launch_colsum(dZ, lddz, N, K, db, part, colsum_blocks(N), s);
+}
+
+template <bool DROP>
+int launch_grad_w(const float *Z, int64_t ldz, const float *b, const float *G, int64_t ldg, float *dW, int64_t lddw,
+                  int64_t N, int K, int n, const MlpDrop &d, float *part, hipStream_t s) {
+    int64_t slices, cps;
+    grad_w_split(N, K, slices, cps);
+    const int ktiles = (K + 31) / 32, kpad = ktiles * 32;
+    for (int m0 = 0; m0 < n; m0 += kWGroup) {
+        const int ng = std::min(n - m0, kWGroup);
+        const dim3 grid(ktiles, static_cast<unsigned>(slices));
+        if (ng > 128)
+            hipLaunchKernelGGL((k_mlp_grad_w<2, DROP>), grid, dim3(256), 0, s, Z, ldz, b, G + m0, ldg, part, N, K, ng, cps, d);
+        else
+            hipLaunchKernelGGL((k_mlp_grad_w<1, DROP>), grid, dim3(256), 0, s, Z, ldz, b, G + m0, ldg, part, N, K, ng, cps, d);
+        const int np = ng > 128 ? 256 : 128;
+        const unsigned rgrid = static_cast<unsigned>((int64_t(ng) * K + 255) / 256);
+        hipLaunchKernelGGL(k_mlp_reduce_w, dim3(rgrid), dim3(256), 0, s, part, static_cast<int>(slices), np, kpad, ng, K,
+                           dW + int64_t(m0) * lddw, lddw);
+    }
+    TGCN_HIP_CHECK(hipGetLastError());
+    return TGCN_OK;
+}
+
+}  // namespace
+}  // namespace tgcn
+
+extern "C" {
+
+int tgcn_mlp_act_linear(const float *Z, int64_t ldz, const float *b, const float *W, int64_t ldw, const float *c, float *C,
+                        int64_t ldc, int64_t N, int k, int n, double p, const uint64_t *seed, int64_t mask_row0,
+                        tgcn_stream stream) {
+    using namespace tgcn;
+    const char *fn = "tgcn_mlp_act_linear";
+    TGCN_CHECK(check_sizes(fn, N, k, n));
+    MlpDrop d{};
+    bool drop = false;
+    TGCN_CHECK(make_mlp_drop(fn, p, seed, mask_row0, d, drop));
+    TGCN_MLP_LD("ldz", ldz, k);
+    TGCN_MLP_LD("ldw", ldw, k);
+    TGCN_MLP_LD("ldc", ldc, n);
+    if (N == 0) return TGCN_OK;                // (an empty tensor's pointer may be NULL)
+    TGCN_MLP_PTR("Z", Z);
+    TGCN_MLP_PTR("b", b);
+    TGCN_MLP_PTR("W", W);
+    TGCN_MLP_PTR("C", C);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return drop ? launch_fwd<true>(Z, ldz, b, W, ldw, c, C, ldc, N, k, n, d, s)
+                : launch_fwd<false>(Z, ldz, b, W, ldw, c, C, ldc, N, k, n, d, s);
+}
+
+size_t tgcn_mlp_act_linear_grad_workspace_bytes(int64_t N, int k, int n) {
+    if (N < 0 || k <= 0 || n <= 0) return 0;
+    return (tgcn::db_floats(N, k) + tgcn::dw_floats(N, k, n)) * sizeof(float);
+}
+
+int tgcn_mlp_act_linear_grad(const float *Z, int64_t ldz, const float *b, const float *W, int64_t ldw, const float *G,
+                             int64_t ldg, float *dZ, int64_t lddz, float *db, float *dW, int64_t lddw, int64_t N, int k,
+                             int n, double p, const uint64_t *seed, int64_t mask_row0, void *workspace,
+                             size_t workspace_bytes, tgcn_stream stream) {
+    using namespace tgcn;
+    const char *fn = "tgcn_mlp_act_linear_grad";
+    TGCN_CHECK(check_sizes(fn, N, k, n));
+    MlpDrop d{};
+    bool drop = false;
+    TGCN_CHECK(make_mlp_drop(fn, p, seed, mask_row0, d, drop));
+    TGCN_MLP_LD("ldz", ldz, k);
+    TGCN_MLP_LD("ldw", ldw, k);
+    TGCN_MLP_LD("ldg", ldg, n);
+    if (dZ) {
+        TGCN_MLP_LD("lddz", lddz, k);
+    }
+    if (dW) {
+        TGCN_MLP_LD("lddw", lddw, k);
+    }
+    if ((dZ == nullptr) != (db == nullptr) && N > 0) {     // (N == 0: dZ has no element and its pointer may be NULL)
+        set_error("%s: dZ and db are computed together: pass both or neither (db is the column sum of dZ)", fn);
+        return TGCN_E_INVALID;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (N == 0) {                              // empty sums; there is no element of dZ
+        if (db) TGCN_HIP_CHECK(hipMemsetAsync(db, 0, sizeof(float) * k, s));
+        if (dW) TGCN_HIP_CHECK(hipMemset2DAsync(dW, sizeof(float) * lddw, 0, sizeof(float) * k, n, s));
+        return TGCN_OK;
+    }
+    TGCN_MLP_PTR("Z", Z);
+    TGCN_MLP_PTR("b", b);
+    TGCN_MLP_PTR("W", W);
+    TGCN_MLP_PTR("G", G);
+    if (!dZ && !dW) {
+        set_error("%s: dZ (with db) and dW are both NULL: nothing to compute", fn);
+        return TGCN_E_INVALID;
+    }
+    const size_t need = tgcn_mlp_act_linear_grad_workspace_bytes(N, k, n);
+    if (!workspace || workspace_bytes < need) {
+        set_error("%s: workspace of %zu bytes, tgcn_mlp_act_linear_grad_workspace_bytes() asks for %zu", fn,
+                  workspace ? workspace_bytes : size_t(0), need);
+        return TGCN_E_INVALID;
+    }
+    float *part_b = static_cast<float *>(workspace);
+    float *part_w = part_b + db_floats(N, k);
+    if (dZ) {
+        TGCN_CHECK(drop ? launch_grad_z<true>(Z, ldz, b, W, ldw, G, ldg, dZ, lddz, db, N, k, n, d, part_b, s)
+                        : launch_grad_z<false>(Z, ldz, b, W, ldw, G, ldg, dZ, lddz, db, N, k, n, d, part_b, s));
+    }
+    if (dW) {
+        TGCN_CHECK(drop ? launch_grad_w<true>(Z, ldz, b, G, ldg, dW, lddw, N, k, n, d, part_w, s)
+                        : launch_grad_w<false>(Z, ldz, b, G, ldg, dW, lddw, N, k, n, d, part_w, s));
+    }
+    return TGCN_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
-"""GCN, EGCN and JumpingKnowledgeNetwork: drop-ins for `textgcn.lib.models.GCN` (textgcn/lib/models.py:6-25), `.EGCN`
-(:28-52) and `.JumpingKnowledgeNetwork` (:55-81; its docstring below).  For GCN and EGCN:
+"""GCN, EGCN, JumpingKnowledgeNetwork and MLP: drop-ins for `textgcn.lib.models.GCN` (textgcn/lib/models.py:6-25), `.EGCN`
+(:28-52), `.JumpingKnowledgeNetwork` (:55-81) and `.MLP` (:83-102; the last two: their docstrings below).  For GCN and EGCN:
 
 Same constructor signature and defaults, same `layers` ModuleList (state_dict keys
 `layers.{i}.weight` (in, out) / `layers.{i}.bias`), same forward: dropout between layers, none
@@ -17,7 +17,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from . import dense, embed
+from . import dense, embed, mlp
 from .conv import GCNConv, features_times, is_sparse_identity, propagate
 from .jk import JumpingKnowledge
 from .plan import _require_cuda
@@ -187,6 +187,76 @@ class EGCN(nn.Module):
             x = layer(x, g.edge_index, g.edge_attr)
             x = self._dropout(x)                 # also after the last layer, as the reference does
         return x
+
+
+# On by default: the hidden layers of MLP -- bias, SELU, dropout and the next Linear -- as ONE product per layer that never
+# stores the activated matrix (pytextgcn_amd/mlp.py).  Off: the same arithmetic composed from `EmbeddingLinear`, torch's
+# SELU and dropout, for A/B runs and tests.
+_FUSED_MLP = True
+
+
+def enable_fused_mlp(on: bool = True) -> bool:
+    """Returns the previous setting."""
+    global _FUSED_MLP
+    was, _FUSED_MLP = _FUSED_MLP, bool(on)
+    return was
+
+
+class MLP(nn.Module):
+    """Drop-in for `textgcn.lib.models.MLP` (textgcn/lib/models.py:83-102), the TF-IDF bag-of-words baseline of
+    MLP_flat.py / MLP_level.py / MLP_label.py: `Linear(in_channels, hidden[0])`, `Linear(hidden[i], hidden[i + 1])` ...,
+    `Linear(hidden[-1], out_channels)`, with SELU and dropout after every layer but the last.
+
+    Same constructor signature, default and assertion (`hidden` is not empty), same attributes: `dropout` is an
+    `nn.Dropout`, `act` an `nn.SELU`, `layers` a ModuleList of Linear modules (`layers.{i}.weight` (out, in),
+    `layers.{i}.bias`, torch's default init: a checkpoint of the reference loads with strict=True).  `forward(x)` takes
+    what the reference's scripts pass: the sparse COO [N, in_channels] TF-IDF matrix of `csr_to_torch` / `append_feats`,
+    or a dense tensor.  The layers are `EmbeddingLinear`s, so every product runs on this package's kernels.
+
+    The fused path: `Z1 = x @ layers[0].weight.t()` on the existing SpMM (or dense) kernel with NO bias added, then one
+    `mlp.act_linear` per remaining layer, which applies the previous layer's bias, SELU and dropout on the way into its own
+    product.  Per hidden layer one N x width matrix is written once and read once, and it is the only thing of that size
+    kept for the backward.  It runs in eval mode and whenever the dropout rate is 0; in training with 0 < rate < 1 only
+    while `enable_fused_dropout()` is on, because the mask is then drawn from the library's random stream, not torch's
+    (the rule `GCN` and `EGCN` follow).  Everything else (rate 1 in training included), and everything after
+    `enable_fused_mlp(False)`, is composed from `EmbeddingLinear`, `torch.selu` and `self.dropout`."""
+
+    def __init__(self, in_channels, out_channels, hidden, dropout=0.5):
+        super().__init__()
+        self.dropout = nn.Dropout(p=dropout)
+        assert hidden
+        ls = [EmbeddingLinear(in_channels, hidden[0])]
+        ls += [EmbeddingLinear(h1, h2) for h1, h2 in zip(hidden, hidden[1:])]
+        ls += [EmbeddingLinear(hidden[-1], out_channels)]
+        self.layers = nn.ModuleList(ls)
+        self.act = nn.SELU()
+
+    def takes_fused_path(self, x) -> bool:
+        """Whether `forward` runs the fused products (see the class docstring).  The answer depends on the mode, the rate
+        and the switches only, never on `x`: the argument is there because GCN and EGCN have it."""
+        p = float(self.dropout.p)
+        if not _FUSED_MLP or any(layer.bias is None for layer in self.layers):
+            return False
+        return not (self.training and p != 0.0 and not (_FUSED_DROPOUT and 0.0 < p < 1.0))
+
+    def forward(self, x):
+        _require_cuda(x, "x")
+        if not self.takes_fused_path(x):
+            last = len(self.layers) - 1
+            for i, layer in enumerate(self.layers):
+                x = layer(x)
+                if i < last:
+                    x = torch.selu(x)
+                    x = self.dropout(x)
+            return x
+        p = float(self.dropout.p) if self.training else 0.0
+        first = self.layers[0]
+        z = features_times(x, first.weight.t(), first.in_features)
+        last = len(self.layers) - 1
+        for i in range(1, len(self.layers)):
+            prev, layer = self.layers[i - 1], self.layers[i]
+            z = mlp.act_linear(z, prev.bias, layer.weight, layer.bias if i == last else None, p)
+        return z
 
 
 class JumpingKnowledgeNetwork(nn.Module):
