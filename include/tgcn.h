@@ -419,6 +419,37 @@ int tgcn_embed_xw_grad(const float *E, int64_t lde, const float *b, const float 
                        double p, const uint64_t *seed, int64_t mask_row0, void *workspace, size_t workspace_bytes,
                        tgcn_stream stream);
 
+/* The same front end on [I_N | H] features (text2graph.py:226-246: the hierarchy features of the per-level scripts).  The
+ * Linear's weight is then ONE parameter [K, N + Fh]: E points at its first N columns and Eh at its last Fh, so lde ==
+ * ldeh == N + Fh in practice (any leading dimensions >= N and >= Fh are taken; no alignment is asked).  Hd [N - h_row0,
+ * Fh] (row stride ldh >= Fh) holds the DENSE rows of H for the nodes i >= h_row0; the nodes below (the word rows) have
+ * no H term, and h_row0 == N means that nobody has one (Hd may then be NULL).  1 <= Fh <= tgcn_embed_xw_h_max_features()
+ * (128).  With
+ *       z(i, k) = (E[k, i] + b[k]) + t(i, k),   t(i, k) = sum over f ascending of H[i, f] Eh[k, f]   (i >= h_row0; else no t)
+ *       a(i, k) = s * keep(i, k) * selu(z(i, k))             (keep, s, selu: as above)
+ *   tgcn_embed_xw_h        C[i, 0:n]  = sum_k a(i, k) W[k, 0:n]
+ *   tgcn_embed_xw_h_grad   dE[k, i]   = s keep(i, k) selu'(z(i, k)) sum_j G[i, j] W[k, j]       (E's layout, stride ldde)
+ *                          db[k]      = sum_i dE[k, i]
+ *                          dEh[k, f]  = sum_{i >= h_row0} dE[k, i] H[i, f]                      (Eh's layout, stride lddeh)
+ *                          dW[k, j]   = sum_i a(i, k) G[i, j]
+ * H gets no gradient.  dE, db and dEh are computed together (all three or none), dW on its own.  t runs on the matrix
+ * cores too, in the registers of the product that consumes it; a wave whose 32 nodes all lie below h_row0 skips it and
+ * computes what tgcn_embed_xw* compute, bit for bit.  The workspace (tgcn_embed_xw_h_grad_workspace_bytes) holds the
+ * partial sums of dW and, after them, those of dEh over a fixed number of slices of the nodes, added in slice order: no
+ * atomics, nothing of size N x K, the same bits every run.  The calls only enqueue on `stream`.  NULL operands, Fh outside
+ * [1, cap], h_row0 outside [0, N], a leading dimension below the width, p outside [0, 1), mask_row0 < 0 and a short
+ * workspace are TGCN_E_INVALID before anything is enqueued; N == 0 launches no kernel; n > 256 runs as column groups. */
+int tgcn_embed_xw_h_max_features(void);
+int tgcn_embed_xw_h(const float *E, int64_t lde, const float *b, const float *Eh, int64_t ldeh, const float *Hd, int64_t ldh,
+                    int64_t h_row0, int Fh, const float *W, int64_t ldw, float *C, int64_t ldc, int64_t N, int K, int n,
+                    double p, const uint64_t *seed, int64_t mask_row0, tgcn_stream stream);
+size_t tgcn_embed_xw_h_grad_workspace_bytes(int64_t N, int K, int n, int Fh);
+int tgcn_embed_xw_h_grad(const float *E, int64_t lde, const float *b, const float *Eh, int64_t ldeh, const float *Hd,
+                         int64_t ldh, int64_t h_row0, int Fh, const float *W, int64_t ldw, const float *G, int64_t ldg,
+                         float *dE, int64_t ldde, float *db, float *dEh, int64_t lddeh, float *dW, int64_t lddw, int64_t N,
+                         int K, int n, double p, const uint64_t *seed, int64_t mask_row0, void *workspace,
+                         size_t workspace_bytes, tgcn_stream stream);
+
 /* ---------------------------------------------------------------------------------------------
  * The middle of the reference's MLP (textgcn/lib/models.py:83-102: `x = dropout(selu(Linear(x)))` feeding the next
  * Linear), as ONE product per layer.  Z [N, k] (row-major, leading dimension ldz >= k) is a layer's stored

@@ -103,6 +103,14 @@ SIGNATURES = {
     "tgcn_embed_xw_grad": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                                    c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_double, c_void_p, c_int64,
                                    c_void_p, c_size_t, c_void_p]),
+    "tgcn_embed_xw_h_max_features": (c_int, []),
+    "tgcn_embed_xw_h": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p,
+                                c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_double, c_void_p, c_int64, c_void_p]),
+    "tgcn_embed_xw_h_grad_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
+    "tgcn_embed_xw_h_grad": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int,
+                                     c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                     c_void_p, c_int64, c_int64, c_int, c_int, c_double, c_void_p, c_int64, c_void_p,
+                                     c_size_t, c_void_p]),
     "tgcn_mlp_act_linear": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64,
                                     c_int, c_int, c_double, c_void_p, c_int64, c_void_p]),
     "tgcn_mlp_act_linear_grad_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),

@@ -231,6 +231,30 @@ def split_identity_block(x: Tensor):
     return rest
 
 
+# The H block as the fused embedding product of EGCN takes it (pytextgcn_amd/embed.py): H is zero on the word rows, so
+# only the rows from the first stored entry on are kept, dense.
+_DENSE_BLOCK_CACHE: dict = {}
+
+
+def dense_hierarchy_block(h: Tensor):
+    """For the sparse [N, F_h] remainder of `split_identity_block`, return `(Hd, h_row0)`: `h_row0` is the first row that
+    holds an entry (N when there is none) and `Hd` the dense float32 rows `[N - h_row0, F_h]` from there on.  Cached per
+    tensor object."""
+    hit = _DENSE_BLOCK_CACHE.get(id(h))
+    if hit is not None and hit[0]() is h:
+        return hit[1]
+    n, fh = h.shape
+    hc = h if h.is_coalesced() else h.coalesce()
+    idx, val = hc.indices(), hc.values()
+    row0 = int(idx[0].min()) if val.numel() else n
+    hd = torch.zeros(n - row0, fh, dtype=torch.float32, device=h.device)
+    if val.numel():
+        hd[idx[0] - row0, idx[1]] = val.to(torch.float32)
+    key = id(h)
+    _DENSE_BLOCK_CACHE[key] = (weakref.ref(h, lambda _, k=key: _DENSE_BLOCK_CACHE.pop(k, None)), (hd, row0))
+    return hd, row0
+
+
 # Sparse feature blocks that are NOT the identity -- the hierarchy block H of [I | H], or a general sparse x --
 # times a dense weight: the same CSR SpMM as the propagate step, on a rectangular operator built once per feature
 # tensor (tgcn_plan_create_coo with its transpose, for the weight gradient H^T @ dXW).

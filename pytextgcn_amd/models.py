@@ -18,7 +18,7 @@ import torch
 from torch import nn
 
 from . import dense, embed, mlp
-from .conv import GCNConv, features_times, is_sparse_identity, propagate
+from .conv import GCNConv, dense_hierarchy_block, features_times, is_sparse_identity, propagate, split_identity_block
 from .jk import JumpingKnowledge
 from .plan import _require_cuda
 
@@ -120,6 +120,20 @@ def enable_fused_embedding(on: bool = True) -> bool:
     return was
 
 
+# Opt-in: the same fused front end on [I_N | H] features (the hierarchy features of the per-level scripts,
+# text2graph.py:226-246): the H term of the Linear joins the pre-activation in registers (`tgcn_embed_xw_h*`).  Off by
+# default: those features then take the composition, as they always did.  `enable_fused_embedding(False)` switches
+# every fused front end off, this one included.
+_FUSED_HIERARCHY = False
+
+
+def enable_fused_hierarchy_embedding(on: bool = True) -> bool:
+    """Returns the previous setting."""
+    global _FUSED_HIERARCHY
+    was, _FUSED_HIERARCHY = _FUSED_HIERARCHY, bool(on)
+    return was
+
+
 class EmbeddingLinear(nn.Linear):
     """`layers[0]` of EGCN: torch's `nn.Linear` (same parameters, same init, same state_dict keys) whose forward runs on
     this package's kernels for every feature format of text2graph.py:226-246 -- `features_times` on `weight.t()`, plus
@@ -144,7 +158,10 @@ class EGCN(nn.Module):
     Exact-identity features take the fused product of `pytextgcn_amd.embed` -- by default in eval mode and whenever
     `dropout` is 0; in training with 0 < dropout < 1 only while `enable_fused_dropout()` is on, because the mask is then
     drawn from the library's random stream, not torch's (the rule `GCN` follows).  Everything else, and everything after
-    `enable_fused_embedding(False)`, is composed from `EmbeddingLinear`, torch's SELU and dropout, and `GCNConv`."""
+    `enable_fused_embedding(False)`, is composed from `EmbeddingLinear`, torch's SELU and dropout, and `GCNConv`.
+
+    After `enable_fused_hierarchy_embedding()` sparse `[I_N | H]` features (H at most `embed.max_hierarchy_features()`
+    columns wide) take the fused product under the same mode and dropout rules."""
 
     def __init__(self, in_channels, out_channels, embedding_dim=2000, n_gcn=2, n_hidden_gcn=64, activation=nn.ReLU,
                  dropout=0.5):
@@ -167,7 +184,12 @@ class EGCN(nn.Module):
             return False
         if self.training and p != 0.0 and not (_FUSED_DROPOUT and 0.0 < p < 1.0):
             return False
-        return is_sparse_identity(x)
+        if is_sparse_identity(x):
+            return True
+        if not _FUSED_HIERARCHY:
+            return False
+        h = split_identity_block(x)
+        return h is not None and h.size(1) <= embed.max_hierarchy_features()
 
     def forward(self, g):
         x = g.x
@@ -175,7 +197,9 @@ class EGCN(nn.Module):
         if self.takes_fused_path(x):
             _require_cuda(x, "g.x")
             plan = first.plan(x, g.edge_index, g.edge_attr)
-            xw = embed.embed_xw(emb.weight, emb.bias, first.weight, float(self.dropout) if self.training else 0.0)
+            hd, h_row0 = (None, 0) if x.size(0) == x.size(1) else dense_hierarchy_block(split_identity_block(x))
+            xw = embed.embed_xw(emb.weight, emb.bias, first.weight, float(self.dropout) if self.training else 0.0,
+                                h=hd, h_row0=h_row0)
             x = propagate(plan, xw, first.bias)
         else:
             x = emb(x)

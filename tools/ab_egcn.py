@@ -6,7 +6,10 @@ temperature drift hits both alike).  The composition is built from the package's
 `features_times`) plus torch's SELU and dropout: `enable_fused_embedding(False)`.  Also reports the peak memory of a train
 step for both (`torch.cuda.max_memory_allocated`) and the forward product's achieved TFLOP/s.
 
-    python tools/ab_egcn.py [--config c2] [--embedding-dim 2000] [--hidden 100] [--dropout 0.5] [--rounds 6]
+    python tools/ab_egcn.py [--config c2] [--embedding-dim 2000] [--hidden 100] [--dropout 0.5] [--rounds 6] [--hierarchy FH]
+
+`--hierarchy FH`: the features are [I_N | H] with one-hot rows of H (FH classes) on the document rows -- the second level
+of a per-level run -- and the A/B is `enable_fused_hierarchy_embedding(True)` (`tgcn_embed_xw_h*`) against the composition.
 """
 import argparse
 import os
@@ -17,7 +20,7 @@ from torch import nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pytextgcn_amd as pkg  # noqa: E402
-from pytextgcn_amd import embed, synth  # noqa: E402
+from pytextgcn_amd import conv, embed, synth  # noqa: E402
 
 CONFIGS = {"c1": (5_000, 60_000, 6), "c2": (100_000, 2_000_000, 64)}      # nodes, edges, classes (BASELINE.json)
 
@@ -28,17 +31,32 @@ ap.add_argument("--hidden", type=int, default=100)
 ap.add_argument("--dropout", type=float, default=0.5)
 ap.add_argument("--rounds", type=int, default=6)
 ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--hierarchy", type=int, default=0, metavar="FH",
+                help="[I | H] features: FH one-hot hierarchy columns on the document rows (0: identity features)")
 args = ap.parse_args()
 
 dev = torch.device("cuda:0")
 N, n_edges, n_classes = CONFIGS[args.config]
 K, h, p = args.embedding_dim, args.hidden, args.dropout
 g0 = synth.word_doc_graph(N, n_edges, seed=44, n_classes=n_classes)
+FH = args.hierarchy
+HD, H_ROW0 = None, 0
+if FH:
+    V = max(2, int(N * 0.1))                              # synth.word_doc_graph: the words come first, then the documents
+    docs = torch.arange(V, N)
+    cls = torch.randint(0, FH, (N - V,), generator=torch.Generator().manual_seed(7))
+    ar = torch.arange(N)
+    g0.x = torch.sparse_coo_tensor(torch.cat([torch.stack([ar, ar]), torch.stack([docs, N + cls])], 1), torch.ones(2 * N - V),
+                                   (N, N + FH)).coalesce()
 g = pkg.Data(**{k: getattr(g0, k) for k in g0.keys}).to(dev)
 torch.manual_seed(0)
-model = pkg.EGCN(N, n_classes, embedding_dim=K, n_hidden_gcn=h, dropout=p).to(dev).float()
+model = pkg.EGCN(N + FH, n_classes, embedding_dim=K, n_hidden_gcn=h, dropout=p).to(dev).float()
 crit = nn.CrossEntropyLoss()
 pkg.enable_fused_dropout(True)
+if FH:
+    HD, H_ROW0 = conv.dense_hierarchy_block(conv.split_identity_block(g.x))
+# the switch of the A/B: with [I | H] features the hierarchy switch (the master switch stays on), else the master switch
+switch = pkg.enable_fused_hierarchy_embedding if FH else pkg.enable_fused_embedding
 
 
 def train_step():
@@ -55,12 +73,13 @@ def eval_forward():
 
 def product_forward():
     with torch.no_grad():
-        embed.embed_xw_forward(model.layers[0].weight, model.layers[0].bias, model.layers[1].weight)
+        embed.embed_xw_forward(model.layers[0].weight, model.layers[0].bias, model.layers[1].weight, h=HD, h_row0=H_ROW0)
 
 
 def product_forward_dropout():
     with torch.no_grad():
-        embed.embed_xw_forward(model.layers[0].weight, model.layers[0].bias, model.layers[1].weight, p, SEED)
+        embed.embed_xw_forward(model.layers[0].weight, model.layers[0].bias, model.layers[1].weight, p, SEED, h=HD,
+                               h_row0=H_ROW0)
 
 
 SEED = torch.tensor([20240607], dtype=torch.int64, device=dev)
@@ -70,7 +89,7 @@ cases = [("train step", train_step, True), ("train step", train_step, False), ("
 times = {(name, fused): [] for name, _, fused in cases}
 for rnd in range(args.rounds + 1):                       # round 0 = warm-up (plan build, allocator)
     for name, fn, fused in cases:
-        was = pkg.enable_fused_embedding(fused)
+        was = switch(fused)
         try:
             fn()
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.reps + 1)]
@@ -80,13 +99,13 @@ for rnd in range(args.rounds + 1):                       # round 0 = warm-up (pl
                 ev[i + 1].record()
             torch.cuda.synchronize()
         finally:
-            pkg.enable_fused_embedding(was)
+            switch(was)
         if rnd:
             times[(name, fused)] += [ev[i].elapsed_time(ev[i + 1]) for i in range(args.reps)]
 
 peak = {}
 for fused in (True, False):
-    was = pkg.enable_fused_embedding(fused)
+    was = switch(fused)
     try:
         model.zero_grad(set_to_none=True)
         torch.cuda.synchronize()
@@ -96,10 +115,12 @@ for fused in (True, False):
         torch.cuda.synchronize()
         peak[fused] = (torch.cuda.max_memory_allocated(), torch.cuda.max_memory_allocated() - base)
     finally:
-        pkg.enable_fused_embedding(was)
+        switch(was)
 
 print(f"ab_egcn: {torch.cuda.get_device_name(0)}; config {args.config}: N={N} edges={n_edges} classes={n_classes}; "
-      f"embedding_dim={K} hidden={h} dropout={p}; {args.rounds} rounds x {args.reps} repetitions, interleaved")
+      f"embedding_dim={K} hidden={h} dropout={p}; "
+      + (f"[I | H] features, Fh={FH} one-hot on the {N - H_ROW0} document rows (h_row0={H_ROW0}); " if FH else "")
+      + f"{args.rounds} rounds x {args.reps} repetitions, interleaved")
 
 
 def stats(ts):
