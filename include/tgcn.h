@@ -298,6 +298,33 @@ int tgcn_masked_ce_grad(const float *logits, int64_t ld, int64_t n_rows, int n_c
  * device scalar the host cannot read without a synchronisation (`loss.backward()` seeds it with 1). */
 int tgcn_scale_by_device_scalar(float *x, int64_t n, const float *scale_dev, tgcn_stream stream);
 
+/* tgcn_grouped_ce -- the losses of the per-label strategy (perlabel_amazon.py:90-155: one classifier per top-level label,
+ * each trained on its label's documents with their classes relabelled to 0..C_k-1) for ALL K classifiers in one pass over
+ * their concatenated logits [n_rows, n_cols] (fp32, stride ld).  Group k owns the column segment [seg_start[k],
+ * seg_start[k] + seg_width[k]): increasing, non-overlapping, width >= 1, gaps (pad columns) allowed, any alignment.
+ *   group  int32 [n_rows]   the segment a row is TRAINED on, -1 = none (word nodes)
+ *   target int64 [n_rows]   the LOCAL class in [0, seg_width[group]); read only where mask is set and group >= 0
+ *   mask   uint8/bool       inv_count fp32 [K] (device) = 1 / selected rows of the group, 0 for a group with none
+ *   route  int32 [n_rows] or NULL (= group): the segment the PREDICTION is taken in (eval_perlabel.py:73)
+ *   class_map int64 [n_cols] or NULL: column -> global class id (the `mapping` of perlabel_amazon.py:107,159)
+ * Results (loss_k, dlogits, dbias and pred may be NULL; dbias needs dlogits):
+ *   loss    device scalar = sum over the non-empty groups of loss_k;  loss_k [K] = the group's mean CE, NaN when empty
+ *   dlogits [n_rows, n_cols] stride ldd: (softmax - one-hot) * inv_count[group] inside the row's segment, exactly 0.0f in
+ *           every other column, on every unselected row and on every row of group -1
+ *   dbias   [n_cols] = column sums of dlogits;  pred int64 [n_rows] = seg_start[route] + argmax inside the route's
+ *           segment (first index on ties), through class_map when given, -1 where route is -1
+ * The segments are given twice: seg_start / seg_width on the DEVICE for the kernel, and the same values on the HOST, from
+ * which the call validates them (TGCN_E_INVALID before anything is enqueued: overlapping or decreasing segments, one past
+ * n_cols, ld < n_cols, more than 128 groups) without reading device memory.  Deterministic (fixed-order reductions, no
+ * atomics); only enqueues on `stream`.  Workspace: tgcn_grouped_ce_workspace_bytes. */
+size_t tgcn_grouped_ce_workspace_bytes(int64_t n_rows, int n_cols, int n_groups);
+int tgcn_grouped_ce(const float *logits, int64_t ld, int64_t n_rows, int n_cols, int n_groups,
+                    const int32_t *seg_start_host, const int32_t *seg_width_host, const int32_t *seg_start,
+                    const int32_t *seg_width, const int32_t *group, const int32_t *route, const int64_t *target,
+                    const uint8_t *mask, const float *inv_count, const int64_t *class_map, float *loss, float *loss_k,
+                    float *dlogits, int64_t ldd, float *dbias, int64_t *pred, void *workspace, size_t workspace_bytes,
+                    tgcn_stream stream);
+
 /* tgcn_adam_step -- one `torch.optim.Adam(..., amsgrad=...)` update of a flat fp32 tensor
  * (flat_amazon.py:89,106), torch's single-tensor formula op for op, fused into one pass.
  * max_exp_avg_sq = NULL means amsgrad=False.  `step` is the 1-based step count AFTER increment. */

@@ -41,6 +41,19 @@ def _rowmajor4(t: Tensor) -> Tensor:
     return t
 
 
+def _unit_cols(t: Tensor) -> Tensor:
+    """The small operand as the kernels take it: unit column stride, any row stride (a column slice is not copied)."""
+    return t if t.stride(1) == 1 else t.contiguous()
+
+
+def _check_out(fn: str, out: Tensor, rows: int, cols: int, like: Tensor, aligned: bool) -> Tensor:
+    if out.shape != (rows, cols) or out.dtype != torch.float32 or out.device != like.device or (rows and out.stride(1) != 1) \
+            or (aligned and (out.stride(0) % 4 != 0 or out.data_ptr() % 16 != 0)):
+        raise ValueError(f"{fn}: `out` must be a float32 [{rows}, {cols}] device tensor with unit column stride"
+                         + (" and 16-byte rows" if aligned else ""))
+    return out
+
+
 def _check_seed(seed: Tensor, dev) -> None:
     if seed.dtype != torch.int64 or seed.numel() != 1 or seed.device != dev:
         raise TypeError("dropout seed must be a one-element int64 tensor on the operand's device")
@@ -72,7 +85,7 @@ def gemm_nn(a: Tensor, b: Tensor, p: float = 0.0, seed: Tensor = None, record_ma
     cannot record it.  `keys` = (split, key0, key1): which mask row a row of `a` is (see `_row_keys`).  `out`: a
     float32 [N, n] result buffer of the caller's (unit column stride, rows 16-byte aligned)."""
     lib = _lib.load()
-    a, b = _rowmajor4(a), b.contiguous()
+    a, b = _rowmajor4(a), _unit_cols(b)
     N, k = a.shape
     n = b.size(1)
     if out is None:
@@ -100,22 +113,28 @@ def gemm_nn(a: Tensor, b: Tensor, p: float = 0.0, seed: Tensor = None, record_ma
 
 
 def gemm_nt(a: Tensor, b: Tensor, p: float = 0.0, seed: Tensor = None, note_colsums: bool = False,
-            mask: Tensor = None, keys=None) -> Tensor:
+            mask: Tensor = None, keys=None, out: Tensor = None, sums_out: Tensor = None) -> Tensor:
     """a [N, k] @ b[n, k]^T; with `seed` the [N, n] result is masked and scaled (dropout backward).
     `note_colsums`: the kernel also sums the columns of the result it stores and the sums are recorded for
     `plan.colsum` (the result is a gradient on its way to a layer with a bias).  `mask` (with `seed` and `note_colsums`):
-    the record `gemm_nn(..., record_mask=True)` left of the same dropout -- same bits, no hashing."""
+    the record `gemm_nn(..., record_mask=True)` left of the same dropout -- same bits, no hashing.
+    `out`: a float32 [N, n] result buffer of the caller's (unit column stride; a column slice of a wider matrix).
+    `sums_out` (with `note_colsums` and `out`): the [n] buffer that takes the column sums; NO note is left then -- the
+    caller, who owns the wider matrix, leaves one for the whole of it."""
     lib = _lib.load()
-    a, b = _rowmajor4(a), b.contiguous()
+    a, b = _rowmajor4(a), _unit_cols(b)
     N, k = a.shape
     n = b.size(0)
-    c = torch.empty(N, n, dtype=torch.float32, device=a.device)
+    c = torch.empty(N, n, dtype=torch.float32, device=a.device) if out is None else _check_out("gemm_nt", out, N, n, a, False)
     args = (a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), c.data_ptr(), c.stride(0), N, k, n)
     if note_colsums:
         from .plan import note_colsum
         if seed is not None:
             _check_seed(seed, a.device)
-        sums = torch.empty(n, dtype=torch.float32, device=a.device)
+        if sums_out is not None and (out is None or sums_out.shape != (n,) or sums_out.dtype != torch.float32
+                                     or sums_out.device != a.device or not sums_out.is_contiguous()):
+            raise ValueError("gemm_nt: `sums_out` goes with `out` and is a contiguous float32 [n] device tensor")
+        sums = torch.empty(n, dtype=torch.float32, device=a.device) if sums_out is None else sums_out
         ws_bytes = lib.tgcn_gemm_nt_colsum_workspace_bytes(n)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device)
         with _row_keys(lib, keys if seed is not None else None):
@@ -128,7 +147,8 @@ def gemm_nt(a: Tensor, b: Tensor, p: float = 0.0, seed: Tensor = None, note_cols
             else:
                 _lib.check(lib.tgcn_gemm_nt_colsum(*args, float(p), seed.data_ptr() if seed is not None else None,
                                                    sums.data_ptr(), ws.data_ptr(), ws_bytes, _stream_ptr(a.device)))
-        note_colsum(c, sums)
+        if sums_out is None:
+            note_colsum(c, sums)
         return c
     if seed is None:
         _lib.check(lib.tgcn_gemm_nt(*args, _stream_ptr(a.device)))
@@ -139,9 +159,11 @@ def gemm_nt(a: Tensor, b: Tensor, p: float = 0.0, seed: Tensor = None, note_cols
     return c
 
 
-def gemm_tn(a: Tensor, g: Tensor, p: float = 0.0, seed: Tensor = None, mask: Tensor = None, keys=None) -> Tensor:
+def gemm_tn(a: Tensor, g: Tensor, p: float = 0.0, seed: Tensor = None, mask: Tensor = None, keys=None,
+            out: Tensor = None) -> Tensor:
     """a[N, k]^T @ g[N, n]; with `seed`: dropout(a, p)^T @ g; `mask`: the record `gemm_nn(..., record_mask=True)` left
-    of the same dropout (same bits as hashing from the seed, without the hashing)."""
+    of the same dropout (same bits as hashing from the seed, without the hashing).  `out`: a float32 [k, n] result buffer
+    of the caller's (unit column stride; a column slice of a wider matrix)."""
     lib = _lib.load()
     if a.stride(1) != 1:
         a = a.contiguous()
@@ -149,7 +171,7 @@ def gemm_tn(a: Tensor, g: Tensor, p: float = 0.0, seed: Tensor = None, mask: Ten
         g = g.contiguous()
     N, k = a.shape
     n = g.size(1)
-    c = torch.empty(k, n, dtype=torch.float32, device=a.device)
+    c = torch.empty(k, n, dtype=torch.float32, device=a.device) if out is None else _check_out("gemm_tn", out, k, n, a, False)
     ws_bytes = lib.tgcn_gemm_tn_workspace_bytes(N, k, n)
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=a.device)
     args = (a.data_ptr(), a.stride(0), g.data_ptr(), g.stride(0), c.data_ptr(), c.stride(0), N, k, n)

@@ -170,3 +170,201 @@ def masked_cross_entropy(logits: Tensor, target: Tensor, mask: Tensor, count=Non
         return _MaskedCE.apply(logits, target, mask, count, return_pred)
     loss, _, pred = _launch(logits, target, mask, False, count, return_pred)
     return (loss, pred) if return_pred else loss
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Grouped masked cross-entropy: the K losses of the per-label strategy (perlabel_amazon.py:90-155) in one pass
+# ---------------------------------------------------------------------------------------------------------------------
+_SEGMENTS: dict = {}
+
+
+class Segments:
+    """Column segments of K concatenated classifiers: host lists (validation, Python-side arithmetic) and the int32 device
+    copies the kernel reads.  `Segments.of(starts, widths, device)` caches one object per distinct layout and device."""
+
+    def __init__(self, starts, widths, device):
+        self.starts, self.widths = tuple(int(s) for s in starts), tuple(int(w) for w in widths)
+        if len(self.starts) != len(self.widths) or not self.starts:
+            raise ValueError("seg_start and seg_width must hold one entry per group (at least one group)")
+        self.K = len(self.starts)
+        self.host_start = (ctypes.c_int32 * self.K)(*self.starts)
+        self.host_width = (ctypes.c_int32 * self.K)(*self.widths)
+        self.dev_start = torch.tensor(self.starts, dtype=torch.int32, device=device)
+        self.dev_width = torch.tensor(self.widths, dtype=torch.int32, device=device)
+
+    @staticmethod
+    def of(starts, widths, device) -> "Segments":
+        if isinstance(starts, Segments):
+            return starts
+        as_list = lambda v: v.tolist() if isinstance(v, Tensor) else list(v)       # (a device tensor: one copy, then cached)
+        key = (tuple(as_list(starts)), tuple(as_list(widths)), str(device))
+        hit = _SEGMENTS.get(key)
+        if hit is None:
+            if len(_SEGMENTS) >= 64:
+                _SEGMENTS.clear()
+            hit = _SEGMENTS[key] = Segments(key[0], key[1], device)
+        return hit
+
+
+_GROUP_STATS: dict = {}
+
+
+def _group_stats(mask: Tensor, group: Tensor, target: Tensor, seg: Segments):
+    """(selected rows per group [K] on the host, `keep` = mask & (group >= 0) on the device) for static masks and groups:
+    one device sync per distinct (mask, group, target) objects and versions, as `_mask_count` / `_check_targets` do.  The
+    same visit checks that the groups lie in [-1, K) and the targets of the selected rows in [0, width of their group)."""
+    import weakref
+    key = (id(mask), id(group), id(target), seg.starts, seg.widths)
+    versions = (mask._version, group._version, target._version)
+    hit = _GROUP_STATS.get(key)
+    if hit is not None and hit[0]() is mask and hit[1]() is group and hit[2]() is target and hit[3] == versions:
+        return hit[4], hit[5]
+    K = seg.K
+    if bool(((group < -1) | (group >= K)).any().item()):
+        raise IndexError(f"group holds an index outside [-1, {K})")
+    keep = mask & (group >= 0)
+    gk = group[keep].long()
+    width = seg.dev_width.long()[gk]
+    tk = target[keep]
+    bad = (tk < 0) | (tk >= width)
+    if bool(bad.any().item()):
+        i = int(torch.nonzero(bad)[0].item())
+        raise IndexError(f"Target {int(tk[i].item())} is out of bounds for the {int(width[i].item())} classes of group "
+                         f"{int(gk[i].item())} (on a row selected by the mask)")
+    counts = torch.bincount(gk, minlength=K).tolist()
+    try:
+        drop = lambda _, k=key: _GROUP_STATS.pop(k, None)
+        _GROUP_STATS[key] = (weakref.ref(mask, drop), weakref.ref(group, drop), weakref.ref(target, drop), versions, counts, keep)
+    except TypeError:
+        pass
+    return counts, keep
+
+
+_INV_COUNTS: dict = {}
+
+
+def _inv_counts(counts, device) -> Tensor:
+    key = (tuple(int(c) for c in counts), str(device))
+    hit = _INV_COUNTS.get(key)
+    if hit is None:
+        if len(_INV_COUNTS) >= 64:
+            _INV_COUNTS.clear()
+        hit = _INV_COUNTS[key] = torch.tensor([1.0 / c if c else 0.0 for c in key[0]], dtype=torch.float32, device=device)
+    return hit
+
+
+def _launch_grouped(logits: Tensor, target: Tensor, mask: Tensor, group: Tensor, seg: Segments, counts, want_grad: bool,
+                    want_pred: bool, route, class_map):
+    lib = _lib.load()
+    _require_cuda(logits, "logits")
+    if logits.dtype != torch.float32 or logits.dim() != 2:
+        raise TypeError("logits must be a 2-D float32 tensor")
+    n, C = logits.shape
+    if target.shape != (n,) or mask.shape != (n,) or group.shape != (n,) or (route is not None and route.shape != (n,)):
+        raise ValueError("target, mask, group and route must have one entry per logits row")
+    if mask.dtype != torch.bool or group.dtype != torch.int32 or (route is not None and route.dtype != torch.int32):
+        raise TypeError("mask must be a bool tensor, group and route int32 tensors")
+    if target.dtype != torch.int64:
+        raise TypeError("target must be an int64 tensor")
+    if class_map is not None and (class_map.dtype != torch.int64 or class_map.shape != (C,)):
+        raise TypeError("class_map must be an int64 tensor with one entry per logits column")
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    keep = None
+    if counts is None or (want_grad and not torch.cuda.is_current_stream_capturing()):
+        # (no sync inside a HIP-graph capture: pass `counts`; the check ran on the eager warm-up step.  A forward-only call
+        # that brings its counts is not checked on the host: the kernel never reads outside a row, a class index outside
+        # the segment makes the group's loss NaN)
+        own, keep = _group_stats(mask, group, target, seg)
+        counts = own if counts is None else counts
+    if len(counts) != seg.K:
+        raise ValueError("counts must hold one entry per group")
+    inv = _inv_counts(counts, logits.device)
+    target, mask, group = target.contiguous(), mask.contiguous(), group.contiguous()
+    route = None if route is None else route.contiguous()
+    class_map = None if class_map is None else class_map.contiguous()
+    dev = logits.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    loss_k = torch.empty(seg.K, dtype=torch.float32, device=dev)
+    pred = torch.empty(n, dtype=torch.int64, device=dev) if want_pred else None
+    dlogits = dbias = None
+    if want_grad:
+        dlogits = alloc_padded(n, C, dev)
+        C4 = (C + 3) & ~3
+        dbias = torch.zeros(C4, dtype=torch.float32, device=dev)[:C] if C4 != C else \
+            torch.empty(C, dtype=torch.float32, device=dev)
+    ws_bytes = lib.tgcn_grouped_ce_workspace_bytes(n, C, seg.K)
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    _lib.check(lib.tgcn_grouped_ce(
+        logits.data_ptr(), logits.stride(0), n, C, seg.K, seg.host_start, seg.host_width, seg.dev_start.data_ptr(),
+        seg.dev_width.data_ptr(), group.data_ptr(), ptr(route), target.data_ptr(), mask.data_ptr(), inv.data_ptr(),
+        ptr(class_map), loss.data_ptr(), loss_k.data_ptr(), ptr(dlogits), dlogits.stride(0) if want_grad else C,
+        ptr(dbias), ptr(pred), ws.data_ptr(), ws.numel(), _stream_ptr(dev)))
+    return loss, loss_k, (dlogits, dbias) if want_grad else None, pred, keep
+
+
+class _GroupedCE(torch.autograd.Function):
+    """Built like `_MaskedCE`: the gradient buffer is scaled in place by the incoming device scalar (single use), and the
+    backward leaves the column sums and the zero rows of the gradient for the propagate step that consumes it."""
+
+    @staticmethod
+    def forward(ctx, logits, target, mask, group, seg, counts, want_pred, route, class_map):
+        loss, loss_k, grads, pred, keep = _launch_grouped(logits.detach(), target, mask, group, seg, counts,
+                                                          ctx.needs_input_grad[0], want_pred, route, class_map)
+        ctx.save_for_backward(*(grads if grads is not None else ()))
+        ctx.keep = keep
+        ctx.versions = (mask, mask._version, group, group._version)
+        if not want_pred:
+            ctx.mark_non_differentiable(loss_k)
+            return loss, loss_k
+        ctx.mark_non_differentiable(loss_k, pred)        # (one call: a second one would replace the first)
+        return loss, loss_k, pred
+
+    @staticmethod
+    def backward(ctx, grad_out: Tensor, *_):
+        # (asked before the saved tensors are: torch would refuse them with a message about an in-place edit)
+        if getattr(ctx, "_tgcn_used", False):
+            raise RuntimeError("grouped_masked_cross_entropy: backward was already run through this loss (its gradient "
+                               "buffer is scaled in place); recompute the loss instead of retain_graph=True")
+        ctx._tgcn_used = True
+        dlogits, dbias = ctx.saved_tensors
+        base = padded_base(dlogits, (dlogits.size(1) + 3) & ~3)
+        if grad_out.is_cuda and grad_out.dtype == torch.float32 and grad_out.numel() == 1:
+            _scale_by_device_scalar(base if base is not None else dlogits, grad_out)
+            _scale_by_device_scalar(dbias, grad_out)
+        else:
+            dlogits.mul_(grad_out)
+            dbias.mul_(grad_out)
+        if base is not None:
+            note_colsum(base, torch.as_strided(dbias, (base.size(1),), (1,)))
+        else:
+            note_colsum(dlogits, dbias)
+        # rows outside mask & (group >= 0) are exactly zero -- true for the mask and groups of the forward pass only
+        mask, mv, group, gv = ctx.versions
+        if ctx.keep is not None and mask._version == mv and group._version == gv:
+            note_zero_rows(base if base is not None else dlogits, ctx.keep)
+        return (dlogits,) + (None,) * 8
+
+
+def grouped_masked_cross_entropy(logits: Tensor, target: Tensor, mask: Tensor, group: Tensor, seg_start, seg_width,
+                                 counts=None, return_pred: bool = False, route: Tensor = None, class_map: Tensor = None):
+    """The K losses of the per-label strategy (perlabel_amazon.py:130-137, one `CrossEntropyLoss('mean')` per top-level
+    label) on the concatenated logits of the K classifiers, as ONE HIP kernel (libtgcn.so `tgcn_grouped_ce`).
+
+    Row r is trained on the column segment `[seg_start[k], seg_start[k] + seg_width[k])` of its group `k = group[r]` (int32;
+    -1 = none) with the LOCAL class `target[r]` (int64, read where `mask[r]` and `group[r] >= 0`).  Returns `(loss, loss_k)`:
+    `loss_k[k] = CrossEntropyLoss('mean')(logits[sel_k][:, seg_k], target[sel_k])` with `sel_k = mask & (group == k)` (NaN
+    for an empty selection, as torch's mean over nothing) and `loss` = the sum of the others -- the objective whose
+    gradient is the K separate trainings' gradients side by side.  `loss` carries the gradient; `loss_k` is for reporting.
+
+    `seg_start` / `seg_width`: sequences of ints (or a `Segments`): increasing, non-overlapping, width >= 1; gaps allowed.
+    `counts`: the selected rows per group when the caller knows them (default: counted once per mask / group object).
+    `return_pred=True` adds `pred` (int64 [N]): `seg_start[q] + argmax(logits[r, seg_q])` with `q = route[r]` (default: the
+    group; eval_perlabel.py:73 routes by the top-level classifier's label), mapped through `class_map` (int64 [n_cols],
+    column -> global class: the `mapping` of perlabel_amazon.py:107) when given, -1 where `q` is -1."""
+    seg = Segments.of(seg_start, seg_width, logits.device)
+    if logits.requires_grad and torch.is_grad_enabled():
+        return _GroupedCE.apply(logits, target, mask, group, seg, counts, return_pred, route, class_map)
+    loss, loss_k, _, pred, _ = _launch_grouped(logits, target, mask, group, seg, counts, False, return_pred, route, class_map)
+    return (loss, loss_k, pred) if return_pred else (loss, loss_k)

@@ -1,6 +1,8 @@
 """`textgcn.lib.models` import path (flat_amazon.py:14 `from textgcn.lib.models import *`;
 perlevel_amazon.py:14 `from textgcn.lib.models import JumpingKnowledgeNetwork, GCN, EGCN`;
-MLP_flat.py `from textgcn.lib.models import MLP`)."""
+MLP_flat.py `from textgcn.lib.models import MLP`).  `PerLabelGCN` has no counterpart there: it is the K `GCN`s of
+perlabel_amazon.py:113 as one network (pytextgcn_amd/perlabel.py)."""
 from ..models import EGCN, GCN, MLP, JumpingKnowledgeNetwork
+from ..perlabel import PerLabelGCN
 
-__all__ = ["GCN", "EGCN", "JumpingKnowledgeNetwork", "MLP"]
+__all__ = ["GCN", "EGCN", "JumpingKnowledgeNetwork", "MLP", "PerLabelGCN"]
