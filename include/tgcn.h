@@ -478,6 +478,37 @@ int tgcn_embed_xw_h_grad(const float *E, int64_t lde, const float *b, const floa
                          size_t workspace_bytes, tgcn_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The first GCNConv's x @ W on [I_N | H] features for the plain GCN of the per-level scripts (perlevel_amazon.py:122,156;
+ * both set `model = GCN`).  Additive to ABI 7.  W [N + Fh, F] (row stride ldw >= F) is the layer's whole weight and
+ * Wh = W + N * ldw its last Fh rows, so X @ W = W[0:N] + H @ Wh.  The nodes below h_row0 (the word rows) have no
+ * hierarchy term; h_row0 == N means that nobody has one.  1 <= Fh <= tgcn_hier_max_features() (128), F >= 1.
+ *   tgcn_hier_xw        C[i, 0:F] = W[i, 0:F] + t(i, :),  i in [0, N)                    C [N, F] stride ldc
+ *     TGCN_HIER_ONEHOT  cls int32 [N - h_row0]: t(i, :) = Wh[cls[i - h_row0], :] (formed as Wh + 0).  A class id outside
+ *                       [0, Fh) contributes nothing: it is skipped on the device, never read through (the rule of
+ *                       tgcn_rows_gather).  Hd is not read.
+ *     TGCN_HIER_DENSE   Hd [N - h_row0, Fh] stride ldh >= Fh: t(i, c) = fmaf(Hd[i, f], Wh[f, c], t) over f ascending from
+ *                       t = 0, then C = W + t: a one-hot Hd gives the ONEHOT form's bits exactly (finite weights).  cls
+ *                       is not read.  The rows below h_row0 are a copy of W's rows.
+ *   tgcn_hier_xw_grad   for G = dC [N, F] stride ldg and dW [N + Fh, F] stride lddw:  dW[0:N] = G, and
+ *     TGCN_HIER_ONEHOT  dW[N + f, :] = sum over the rows i >= h_row0 with cls = f of G[i, :]; a class without a row gets
+ *                       exact zeros.  The document rows are cut into a fixed number of slices whose partial sums
+ *                       [slices, Fh, F] -- nothing of size N x F -- go to the workspace
+ *                       (tgcn_hier_xw_grad_workspace_bytes) and are added in slice order: no atomics, the same bits
+ *                       every run.
+ *     TGCN_HIER_DENSE   dW[N:] is NOT written: it is Hd^T @ G[h_row0:], the caller's tgcn_gemm_tn.  No workspace.
+ * H gets no gradient.  Streaming kernels in float4 lanes where F, the strides and the pointers allow, in dword lanes with
+ * the same results otherwise.  The calls only enqueue on `stream`; all offsets are 64-bit.  NULL operands, Fh outside
+ * [1, cap], h_row0 outside [0, N], a leading dimension below the width, a short workspace and an unknown form are
+ * TGCN_E_INVALID before anything is enqueued; N == 0 launches no kernel. */
+enum { TGCN_HIER_ONEHOT = 0, TGCN_HIER_DENSE = 1 };
+int tgcn_hier_max_features(void);
+int tgcn_hier_xw(const float *W, int64_t ldw, int form, const int32_t *cls, const float *Hd, int64_t ldh, int64_t h_row0,
+                 int Fh, float *C, int64_t ldc, int64_t N, int F, tgcn_stream stream);
+size_t tgcn_hier_xw_grad_workspace_bytes(int64_t N, int F, int Fh, int64_t h_row0, int form);
+int tgcn_hier_xw_grad(const float *G, int64_t ldg, int form, const int32_t *cls, int64_t h_row0, int Fh, float *dW,
+                      int64_t lddw, int64_t N, int F, void *workspace, size_t workspace_bytes, tgcn_stream stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The middle of the reference's MLP (textgcn/lib/models.py:83-102: `x = dropout(selu(Linear(x)))` feeding the next
  * Linear), as ONE product per layer.  Z [N, k] (row-major, leading dimension ldz >= k) is a layer's stored
  * pre-activation WITHOUT its bias b [k]; W [n, k] (leading dimension ldw >= k) is the next nn.Linear's weight in torch's

@@ -4,7 +4,7 @@ Mirrors the reference's public surface (textgcn/__init__.py:1-4 exports `Text2Gr
 and `models`): `models.GCN(in, out, n_hidden_gcn=..., dropout=...)(graph)` runs the two GCNConv
 layers as hand-written HIP kernels (libtgcn.so, include/tgcn.h) on an AMD Instinct MI355X.
 """
-from . import embed, functional, jk, mlp, models, optim, perlabel, train
+from . import embed, functional, hier, jk, mlp, models, optim, perlabel, perlevel, train
 from .conv import GCNConv, enable_activation_reuse
 from .data import Data
 from .dense import enable_split_gemms
@@ -12,10 +12,11 @@ from .jk import JumpingKnowledge, enable_fused_jk
 from .models import (EGCN, GCN, MLP, JumpingKnowledgeNetwork, enable_fused_dropout, enable_fused_embedding,
                      enable_fused_hierarchy_embedding, enable_fused_mlp,
                      enable_linear_collapse)
+from .hier import HierarchyFeatures
 from .perlabel import PerLabelGCN
 from .reorder import cluster_documents, reorder_documents
 from .plan import GraphPlan, clear_plan_cache, colsum, enable_zero_row_skipping, plan_for, set_degree_sum
 from .text2graph import Text2GraphTransformer
 
 __all__ = ["Text2GraphTransformer", "models", "functional", "optim", "train", "GCN", "EGCN", "JumpingKnowledgeNetwork", "JumpingKnowledge", "jk", "enable_fused_jk", "GCNConv", "Data", "GraphPlan", "plan_for", "colsum",
-           "clear_plan_cache", "set_degree_sum", "enable_zero_row_skipping", "enable_activation_reuse", "enable_linear_collapse", "enable_fused_dropout", "enable_fused_embedding", "enable_fused_hierarchy_embedding", "embed", "MLP", "mlp", "enable_fused_mlp", "enable_split_gemms", "reorder_documents", "cluster_documents", "perlabel", "PerLabelGCN"]
+           "clear_plan_cache", "set_degree_sum", "enable_zero_row_skipping", "enable_activation_reuse", "enable_linear_collapse", "enable_fused_dropout", "enable_fused_embedding", "enable_fused_hierarchy_embedding", "embed", "MLP", "mlp", "enable_fused_mlp", "enable_split_gemms", "reorder_documents", "cluster_documents", "perlabel", "PerLabelGCN", "hier", "perlevel", "HierarchyFeatures"]

@@ -18,6 +18,7 @@ OK, E_INVALID, E_RANGE, E_HIP, E_NOMEM, E_WORKSPACE = 0, -1, -2, -3, -4, -5
 NORM_OFF, NORM_ACCURATE, NORM_REFERENCE = 0, 1, 2          # `normalize` of tgcn_plan_create
 DEGREE_ACCURATE, DEGREE_REFERENCE = 0, 1                   # `degree_sum` of tgcn_gcn_norm
 ACT_NONE, ACT_RELU = 0, 1                                   # `act` of tgcn_spmm_act / tgcn_act_grad
+HIER_ONEHOT, HIER_DENSE = 0, 1                              # `form` of tgcn_hier_xw / tgcn_hier_xw_grad
 DEGREE_SUMS = {"accurate": DEGREE_ACCURATE, "reference": DEGREE_REFERENCE}
 
 (Q_N_NODES, Q_N_ROWS, Q_NNZ, Q_NNZ_T, Q_SYMMETRIC, Q_ITEMS, Q_ITEMS_T, Q_LONG_ROWS, Q_LONG_ROWS_T,
@@ -115,6 +116,12 @@ SIGNATURES = {
                                      c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
                                      c_void_p, c_int64, c_int64, c_int, c_int, c_double, c_void_p, c_int64, c_void_p,
                                      c_size_t, c_void_p]),
+    "tgcn_hier_max_features": (c_int, []),
+    "tgcn_hier_xw": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_int64,
+                             c_int, c_void_p]),
+    "tgcn_hier_xw_grad_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int64, c_int]),
+    "tgcn_hier_xw_grad": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_int,
+                                  c_void_p, c_size_t, c_void_p]),
     "tgcn_mlp_act_linear": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64,
                                     c_int, c_int, c_double, c_void_p, c_int64, c_void_p]),
     "tgcn_mlp_act_linear_grad_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),

@@ -15,7 +15,7 @@ from typing import Optional
 import torch
 from torch import Tensor, nn
 
-from . import _lib, dense
+from . import _lib, dense, hier
 from .plan import GraphPlan, _known_colsum, colsum, known_nonzero_rows, padded_base, plan_for, relu_grad_
 
 
@@ -304,7 +304,13 @@ def sparse_times(x: Tensor, w: Tensor) -> Tensor:
 
 def features_times(x: Tensor, w: Tensor, in_channels: int) -> Tensor:
     """X @ w for the feature formats of text2graph.py:226-246 (`w` has `in_channels` rows): dense, the sparse identity,
-    [I | H] and general sparse COO.  Shared by `GCNConv` and by the embedding layer of `pytextgcn_amd.models.EGCN`."""
+    [I | H] and general sparse COO.  Shared by `GCNConv` and by the embedding layer of `pytextgcn_amd.models.EGCN`.
+    A `hier.HierarchyFeatures` -- [I | H] held as class ids or dense rows -- and a row-major `w` run on the kernels of
+    `pytextgcn_amd.hier`; any other layout of `w` (the transposed weight of an `nn.Linear`) takes the sparse road."""
+    if isinstance(x, hier.HierarchyFeatures):
+        if x.size(1) != in_channels:
+            raise ValueError(f"x has {x.size(1)} features, the layer expects {in_channels}")
+        return hier.xw(x, w) if hier.takes(x, w) else features_times(x.to_sparse(), w, in_channels)
     if not x.is_sparse:
         return dense.xw(x, w)             # fp32 MFMA kernels for tall-skinny shapes
     if x.size(1) != in_channels:

@@ -10,6 +10,8 @@ from __future__ import annotations
 
 import torch
 
+from .hier import HierarchyFeatures
+
 
 class Data:
     def __init__(self, x=None, edge_index=None, edge_attr=None, y=None, **kwargs):
@@ -47,7 +49,7 @@ class Data:
 
     def apply(self, func):
         for k, v in list(self.__dict__.items()):
-            if torch.is_tensor(v):
+            if torch.is_tensor(v) or isinstance(v, HierarchyFeatures):    # (the latter moves through its own `to`)
                 setattr(self, k, func(v))
         return self
 

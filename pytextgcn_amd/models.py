@@ -17,7 +17,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from . import dense, embed, mlp
+from . import dense, embed, hier, mlp
 from .conv import GCNConv, dense_hierarchy_block, features_times, is_sparse_identity, propagate, split_identity_block
 from .jk import JumpingKnowledge
 from .plan import _require_cuda
@@ -161,7 +161,8 @@ class EGCN(nn.Module):
     `enable_fused_embedding(False)`, is composed from `EmbeddingLinear`, torch's SELU and dropout, and `GCNConv`.
 
     After `enable_fused_hierarchy_embedding()` sparse `[I_N | H]` features (H at most `embed.max_hierarchy_features()`
-    columns wide) take the fused product under the same mode and dropout rules."""
+    columns wide) take the fused product under the same mode and dropout rules.  A `hier.HierarchyFeatures` of that width
+    takes it without that switch; a wider one is composed on its `to_sparse()`."""
 
     def __init__(self, in_channels, out_channels, embedding_dim=2000, n_gcn=2, n_hidden_gcn=64, activation=nn.ReLU,
                  dropout=0.5):
@@ -180,10 +181,13 @@ class EGCN(nn.Module):
     def takes_fused_path(self, x) -> bool:
         """Whether `forward` on the features `x` runs the fused embedding product (see the class docstring)."""
         p = float(self.dropout)
-        if not (_FUSED_EMBEDDING and x.is_sparse and x.size(1) == self.layers[0].in_features):
+        held = isinstance(x, hier.HierarchyFeatures)       # [I | H] as class ids or dense rows: the type selects the product
+        if not (_FUSED_EMBEDDING and (x.is_sparse or held) and x.size(1) == self.layers[0].in_features):
             return False
         if self.training and p != 0.0 and not (_FUSED_DROPOUT and 0.0 < p < 1.0):
             return False
+        if held:
+            return x.n_features <= embed.max_hierarchy_features()
         if is_sparse_identity(x):
             return True
         if not _FUSED_HIERARCHY:
@@ -197,7 +201,10 @@ class EGCN(nn.Module):
         if self.takes_fused_path(x):
             _require_cuda(x, "g.x")
             plan = first.plan(x, g.edge_index, g.edge_attr)
-            hd, h_row0 = (None, 0) if x.size(0) == x.size(1) else dense_hierarchy_block(split_identity_block(x))
+            if isinstance(x, hier.HierarchyFeatures):
+                hd, h_row0 = x.dense_block(), x.h_row0
+            else:
+                hd, h_row0 = (None, 0) if x.size(0) == x.size(1) else dense_hierarchy_block(split_identity_block(x))
             xw = embed.embed_xw(emb.weight, emb.bias, first.weight, float(self.dropout) if self.training else 0.0,
                                 h=hd, h_row0=h_row0)
             x = propagate(plan, xw, first.bias)
