@@ -3,8 +3,10 @@
 The kernels are held to a float64 restatement (tests/_egcn_ref.py) at the project's bar, max|a - b| / max|b| <= 1e-5
 (BASELINE.json): an fp32 evaluation of the same expressions on the CPU sits at 2.5e-7 .. 6.5e-7 from float64 at
 (N, K, n) = (3000, 2000, 100), (4097, 515, 200), (2000, 2000, 64) with E, b ~ U(+-1/sqrt(N)) and W glorot, so the bar leaves
-more than ten-fold room.  The dropout mask is held to tests/_dropout_hash.py bit for bit.  The model is held to the
-reference's EGCN restated from torch's Linear / selu / dropout and the CPU oracle's GCNConv."""
+more than ten-fold room.  On ROUNDED_CASES (the tile counts that are rounded up to a leaf, operands surrounded by NaN) the
+kernels on an MI355X stay within C 4.2e-7, dE 4.8e-7, db 3.9e-7, dW 4.3e-7, and a column's bits do not depend on the leaf
+that serves it (torch.equal, no tolerance).  The dropout mask is held to tests/_dropout_hash.py bit for bit.  The model is
+held to the reference's EGCN restated from torch's Linear / selu / dropout and the CPU oracle's GCNConv."""
 import math
 import os
 import threading
@@ -76,6 +78,83 @@ def test_kernels_against_float64_without_dropout(cuda, N, K, n, lde_extra, strid
     only_e = embed.embed_xw_backward(E, b, W, G, want_w=False)
     assert only_w[0] is None and only_e[2] is None
     assert torch.equal(only_w[2], dW) and torch.equal(only_e[0], dE) and torch.equal(only_e[1], db)
+
+
+# The forward and dE serve a group of nt = ceil(ng / 32) column tiles on the next leaf of NT in {1, 2, 4, 7, 8}; CASES runs
+# every leaf at its own tile count only.  Here the leaves that are rounded up to: nt = 3 on NT = 4 (n = 65, 96: the fourth
+# tile is all padding), nt = 5 and 6 on NT = 7 (n = 129, 160, 192), seven full tiles (224), the k_embed_grad_w<1 | 2>
+# boundary (128 | 129), a full group followed by a group of one column (256 | 257) and three groups (513).  K in {33, 63}
+# and N in {33, 129} are enough for that: one and two chunks of k, one and two tiles of rows, a tail in each.  Same layout
+# as CASES; about a third with lde > N and column slices for C and G.
+ROUNDED_CASES = [
+    (33, 33, 65, 0, False), (129, 63, 96, 3, True), (129, 63, 65, 0, False), (129, 33, 129, 0, False), (33, 63, 160, 1, True),
+    (129, 63, 192, 0, False), (33, 33, 128, 5, False), (129, 33, 224, 0, False), (33, 63, 256, 0, False),
+    (129, 63, 257, 2, True), (33, 33, 513, 0, False), (129, 63, 513, 7, True),
+]
+
+
+def _in_nan(rows, cols, values, dev, row0=0, col0=0, more_rows=2, more_cols=0):
+    """`values` [rows, cols] as a slice of a buffer that is NaN everywhere else: a read outside the operand shows."""
+    buf = torch.full((row0 + rows + more_rows, col0 + cols + more_cols), float("nan"), device=dev)
+    view = buf[row0:row0 + rows, col0:col0 + cols]
+    view.copy_(values)
+    return view
+
+
+@pytest.mark.parametrize("N,K,n,lde_extra,strided", ROUNDED_CASES)
+def test_rounded_up_leaves_against_float64_among_nan(cuda, N, K, n, lde_extra, strided):
+    """The checks of `test_kernels_against_float64_without_dropout` with every operand surrounded by NaN: Ebuf's columns past
+    N and two rows past K, W's rows past K and columns past n, G's surroundings.  No result may hold one."""
+    E, b, W, G = _operands(N, K, n, 1000 + N + K + n, cuda, lde_extra)
+    E = _in_nan(K, N, E, cuda, more_cols=lde_extra)
+    W = _in_nan(K, n, W, cuda, more_cols=3)
+    assert E.stride(0) == N + lde_extra and W.stride(0) == n + 3
+    out = None
+    if strided:
+        wide = torch.full((N, n + 9), 7.0, device=cuda)
+        out = wide[:, 4:4 + n]
+        G = _in_nan(N, n, G, cuda, col0=2, more_cols=4)
+    else:
+        G = _in_nan(N, n, G, cuda)
+    C = embed.embed_xw_forward(E, b, W, out=out)
+    dE, db, dW = embed.embed_xw_backward(E, b, W, G)
+    torch.cuda.synchronize()
+    assert C.shape == (N, n) and dE.shape == (K, N) and db.shape == (K,) and dW.shape == (K, n)
+    if strided:
+        assert bool((wide[:, :4] == 7.0).all()) and bool((wide[:, 4 + n:] == 7.0).all())   # nothing outside the n columns
+    assert all(bool(torch.isfinite(t).all()) for t in (C, dE, db, dW))
+    tC, tE, tb, tW = R.fused_truth(E, b, W, G)
+    errs = {"C": rel_err(C, tC), "dE": rel_err(dE, tE), "db": rel_err(db, tb), "dW": rel_err(dW, tW)}
+    print(f"embed kernels, rounded-up leaves, N={N} K={K} n={n}: " + ", ".join(f"{k} {v:.2e}" for k, v in errs.items()))
+    assert all(v <= TOL for v in errs.values()), errs
+    only_w = embed.embed_xw_backward(E, b, W, G, want_e=False)
+    only_e = embed.embed_xw_backward(E, b, W, G, want_w=False)
+    assert torch.equal(only_w[2], dW) and torch.equal(only_e[0], dE) and torch.equal(only_e[1], db)
+
+
+_FULL_GROUP = {}
+
+
+def _full_group(dev):
+    """Operands with n = 256 columns -- eight full tiles on NT = 8, dW on k_embed_grad_w<2> -- and their C and dW, once."""
+    if not _FULL_GROUP:
+        E, b, W, G = _operands(129, 63, 256, 4242, dev)
+        _FULL_GROUP["v"] = (E, b, W, G, embed.embed_xw_forward(E, b, W), embed.embed_xw_backward(E, b, W, G, want_e=False)[2])
+    return _FULL_GROUP["v"]
+
+
+@pytest.mark.parametrize("n1", [65, 96, 129, 192])
+def test_bits_of_a_column_do_not_depend_on_the_leaf_that_serves_it(cuda, n1):
+    """By construction, no tolerance.  An element of C is accumulated over k in the same order whichever NT serves its tile
+    (`acc[t]` of k_embed_fwd depends on its own column only), so the forward on W[:, :n1] -- NT = 4 or 7 with padding tiles
+    -- gives the first n1 columns of the forward on all 256.  The row slices of dW are set by N and K alone (`grad_w_split`)
+    and k_embed_reduce_w adds them in slice order under either TW (two slices here), so the same holds for dW with
+    G[:, :n1].  A difference means a leaf sums in another order or reads its padding."""
+    E, b, W, G, C, dW = _full_group(cuda)
+    W1, G1 = W[:, :n1], G[:, :n1]
+    assert W1.stride(0) == 256 and G1.stride(0) == 256
+    assert torch.equal(embed.embed_xw_forward(E, b, W1), C[:, :n1])
+    assert torch.equal(embed.embed_xw_backward(E, b, W1, G1, want_e=False)[2], dW[:, :n1])
 
 
 def _seed_tensor(value, dev):

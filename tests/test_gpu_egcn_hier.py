@@ -4,7 +4,10 @@ and of the switch `enable_fused_hierarchy_embedding` that routes the model to it
 The kernels are held to the float64 restatement of tests/_egcn_hier_ref.py at the project's bar, max|a - b| / max|b| <=
 1e-5 (BASELINE.json; the bar of tests/test_gpu_egcn.py).  An fp32 evaluation of the same expressions on the CPU stays
 within 8.5e-7 of float64 on every shape of CASES and MASK_CASES below, with and without a mask (worst per output: C 6.1e-7,
-dE 8.5e-7 at (333, 515, 300, 6), db 4.0e-7, dEh 6.2e-7, dW 5.8e-7), so the bar leaves more than ten-fold room.  The mask is held to tests/_dropout_hash.py bit for bit, the model
+dE 8.5e-7 at (333, 515, 300, 6), db 4.0e-7, dEh 6.2e-7, dW 5.8e-7), so the bar leaves more than ten-fold room.  On
+ROUNDED_CASES (the tile counts that are rounded up to a leaf, operands surrounded by NaN) the kernels on an MI355X stay
+within C 3.7e-7, dE 7.9e-7, db 3.8e-7, dEh 4.6e-7, dW 5.1e-7, and a column's bits do not depend on the leaf that serves it
+(torch.equal, no tolerance).  The mask is held to tests/_dropout_hash.py bit for bit, the model
 to the reference's EGCN restated from torch's Linear / selu / dropout and the CPU oracle's GCNConv (tests/_egcn_ref.py)."""
 import ctypes
 import math
@@ -20,7 +23,7 @@ from pytextgcn_amd.plan import _stream_ptr
 import _egcn_hier_ref as R
 from _egcn_hier_ref import rel_err
 from _egcn_ref import EGCNRef
-from test_gpu_egcn import _compare, _graph, _seed_tensor, _step, _to
+from test_gpu_egcn import _compare, _graph, _in_nan, _seed_tensor, _step, _to
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -49,9 +52,11 @@ def operands(N, K, n, Fh, h_row0, kind, seed):
 
 
 # (N, K, n, Fh, h_row0, rows of H, strided).  Every N of {0, 31, 333, 1025}, K of {1, 63, 515}, n of {1, 64, 100, 219, 300}
-# (each leaf of the column dispatch; 300 crosses the 256-column group), Fh of {1, 6, 33, 70, 128} plus 16 | 17, the two
-# sides of the registers / reload split of the H operand, and h_row0 of {0, 77 (inside a tile), 128, N} appears; N + Fh is
-# odd nearly everywhere (rows of the weight that are not 16-byte aligned).
+# (each leaf NT in {1, 2, 4, 7, 8} of the column dispatch at its own tile count -- 1, 2, 4, 7 and, in the first group of
+# 300, 8 tiles; 300 crosses the 256-column group), Fh of {1, 6, 33, 70, 128} plus 16 | 17, the two sides of the
+# registers / reload split of the H operand, and h_row0 of {0, 77 (inside a tile), 128, N} appears; N + Fh is odd nearly
+# everywhere (rows of the weight that are not 16-byte aligned).  The tile counts that are ROUNDED UP to a leaf are
+# ROUNDED_CASES' below.
 CASES = [
     (0, 63, 1, 6, 0, "onehot", False), (31, 1, 1, 1, 0, "onehot", False), (31, 63, 64, 6, 31, "softmax", False),
     (333, 63, 64, 6, 77, "onehot", False), (333, 515, 100, 33, 128, "softmax", False),
@@ -62,6 +67,17 @@ CASES = [
     (1025, 515, 64, 16, 700, "softmax", False), (333, 63, 100, 17, 0, "softmax", False),
 ]
 MASK_CASES = [(333, 515, 100, 6, 77, "onehot"), (1025, 63, 219, 33, 128, "softmax"), (1025, 515, 64, 70, 0, "softmax")]
+# The roundings of the column dispatch (forward and dE; the list and its reasons are those of ROUNDED_CASES in
+# tests/test_gpu_egcn.py): nt = 3 tiles on NT = 4 (n = 65, 96), nt = 5 and 6 on NT = 7 (129, 160, 192), seven full tiles
+# (224), the k_embed_h_grad_w<1 | 2> boundary (128 | 129), a full group and a group of one column (256 | 257), three
+# groups (513).  K in {33, 63}, N in {33, 129}, Fh in {6, 17} (either side of the registers / reload split), h_row0 in
+# {0, 77}.
+ROUNDED_CASES = [
+    (33, 33, 65, 6, 0, "onehot", False), (129, 63, 96, 17, 77, "softmax", True), (129, 63, 65, 17, 0, "onehot", False),
+    (129, 33, 129, 6, 77, "onehot", False), (33, 63, 160, 17, 0, "softmax", True), (129, 63, 192, 6, 0, "softmax", False),
+    (33, 33, 128, 17, 0, "onehot", False), (129, 33, 224, 6, 77, "softmax", False), (33, 63, 256, 6, 0, "onehot", False),
+    (129, 63, 257, 17, 77, "onehot", True), (33, 33, 513, 6, 0, "softmax", False), (129, 63, 513, 17, 77, "softmax", True),
+]
 
 
 def _errors(got, want, N):
@@ -105,6 +121,67 @@ def test_kernels_against_float64_without_dropout(cuda, N, K, n, Fh, h_row0, kind
     only_e = embed.embed_xw_backward(wd, bd, Wd, Gd, want_w=False, h=Hdd, h_row0=h_row0)
     assert only_w[0] is None and only_e[2] is None
     assert torch.equal(only_w[2], dW) and torch.equal(only_e[0], dWt) and torch.equal(only_e[1], db)
+
+
+@pytest.mark.parametrize("N,K,n,Fh,h_row0,kind,strided", ROUNDED_CASES)
+def test_rounded_up_leaves_against_float64_among_nan(cuda, N, K, n, Fh, h_row0, kind, strided):
+    """The checks of `test_kernels_against_float64_without_dropout` with the operands surrounded by NaN: two rows past the
+    weight's K, past W's K, past G's N and past H's rows, W's columns past n; `strided` also gives the weight rows longer
+    than N + Fh and makes H, G and the result column slices of wider buffers.  No result may hold a NaN."""
+    weight, b, W, G, Hd = operands(N, K, n, Fh, h_row0, kind, 2000 + N + K + n + Fh)
+    wd = _in_nan(K, N + Fh, weight, cuda, more_cols=3 if strided else 0)
+    Wd = _in_nan(K, n, W, cuda, more_cols=3)
+    bd = b.to(cuda)
+    out = None
+    if strided:
+        wide = torch.full((N, n + 9), 7.0, device=cuda)
+        out = wide[:, 4:4 + n]
+        Gd = _in_nan(N, n, G, cuda, col0=2, more_cols=4)
+        Hdd = _in_nan(N - h_row0, Fh, Hd, cuda, col0=1, more_cols=4)
+        assert wd.stride(0) == N + Fh + 3 and Hdd.stride(0) == Fh + 5
+    else:
+        Gd, Hdd = _in_nan(N, n, G, cuda), _in_nan(N - h_row0, Fh, Hd, cuda)
+    C = embed.embed_xw_forward(wd, bd, Wd, out=out, h=Hdd, h_row0=h_row0)
+    dWt, db, dW = embed.embed_xw_backward(wd, bd, Wd, Gd, h=Hdd, h_row0=h_row0)
+    torch.cuda.synchronize()
+    assert C.shape == (N, n) and dWt.shape == (K, N + Fh) and db.shape == (K,) and dW.shape == (K, n)
+    if strided:
+        assert bool((wide[:, :4] == 7.0).all()) and bool((wide[:, 4 + n:] == 7.0).all())   # nothing outside the n columns
+    assert all(bool(torch.isfinite(t).all()) for t in (C, dWt, db, dW))
+    errs = _errors((C, dWt, db, dW), R.truth(weight, b, Hd, h_row0, W, G), N)
+    print(f"embed_h kernels, rounded-up leaves, N={N} K={K} n={n} Fh={Fh} h_row0={h_row0} {kind}: "
+          + ", ".join(f"{k} {v:.2e}" for k, v in errs.items()))
+    assert all(v <= TOL for v in errs.values()), errs
+    only_w = embed.embed_xw_backward(wd, bd, Wd, Gd, want_e=False, h=Hdd, h_row0=h_row0)
+    only_e = embed.embed_xw_backward(wd, bd, Wd, Gd, want_w=False, h=Hdd, h_row0=h_row0)
+    assert torch.equal(only_w[2], dW) and torch.equal(only_e[0], dWt) and torch.equal(only_e[1], db)
+
+
+_FULL_GROUP = {}
+
+
+def _full_group(dev):
+    """Operands with n = 256 columns -- eight full tiles on NT = 8, dW on k_embed_h_grad_w<2> -- and their C and dW, once."""
+    if not _FULL_GROUP:
+        N, K, Fh, h_row0 = 129, 63, 17, 77
+        t = tuple(x.to(dev) for x in operands(N, K, 256, Fh, h_row0, "softmax", 4242))
+        weight, b, W, G, Hd = t
+        _FULL_GROUP["v"] = t + (h_row0, embed.embed_xw_forward(weight, b, W, h=Hd, h_row0=h_row0),
+                                embed.embed_xw_backward(weight, b, W, G, want_e=False, h=Hd, h_row0=h_row0)[2])
+    return _FULL_GROUP["v"]
+
+
+@pytest.mark.parametrize("n1", [65, 96, 129, 192])
+def test_bits_of_a_column_do_not_depend_on_the_leaf_that_serves_it(cuda, n1):
+    """By construction, no tolerance (the test of the same name in tests/test_gpu_egcn.py has the reasoning; `acc[t]` of
+    k_embed_h_fwd depends on its own column only, the H term enters the activation before any tile is touched, and
+    k_embed_h_grad_w's slices are those of `grad_w_split`): C on W[:, :n1] is C[:, :n1] on all 256 columns, dW with
+    G[:, :n1] is dW[:, :n1]."""
+    weight, b, W, G, Hd, h_row0, C, dW = _full_group(cuda)
+    W1, G1 = W[:, :n1], G[:, :n1]
+    assert W1.stride(0) == 256 and G1.stride(0) == 256
+    assert torch.equal(embed.embed_xw_forward(weight, b, W1, h=Hd, h_row0=h_row0), C[:, :n1])
+    assert torch.equal(embed.embed_xw_backward(weight, b, W1, G1, want_e=False, h=Hd, h_row0=h_row0)[2], dW[:, :n1])
 
 
 @pytest.mark.parametrize("p", [0.3, 0.7])

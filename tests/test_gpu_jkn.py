@@ -4,7 +4,16 @@ The kernels are held to the float64 restatement of tests/_jkn_ref.py (torch.stac
 sum) at the project's bar, max|a - b| / max|b| <= 1e-5 (BASELINE.json).  torch's own float32 LSTM stays at <= 1.4e-7 on the
 output and <= 1.1e-6 on every gradient against float64 on these shapes, so the bar leaves a decade of margin.  The gradient of
 `att.bias` is exact zeros by construction (the softmax is shift invariant); wherever the float32 restatement's rounding noise
-would be the denominator it is compared in absolute terms against the scale of the `att.weight` gradient."""
+would be the denominator it is compared in absolute terms against the scale of the `att.weight` gradient.
+
+The leaf tests run every instantiation k_jk_fwd<1 .. 8> of the fused forward, both workgroup shapes, L up to 8 and, on the
+composed path, H = 257 (`_jkn_ref.LEAF_SHAPES`), with the inputs surrounded by NaN, and hold `alpha` -- which the kernel
+writes and the whole backward is built on -- to float64 on both paths.  On those shapes plus (257, 2), at N in {33, 65, 129},
+torch's float32 LSTM on the CPU is within 1.8e-7 (out), 2.0e-7 (alpha) and 2.6e-6 (gradients; the worst at L = 8, N = 65)
+of float64, so the bar leaves four-fold room over a faithful float32 evaluation.  The kernels on an MI355X: out <= 2.3e-7
+(the composed path at C = 24, L = 8; the fused kernel 1.8e-7), alpha <= 1.8e-7, every gradient <= 1.0e-6 (the biases at
+C = 11, L = 6, N = 1), and the rows of alpha sum to 1 within 1.25 ulp.  tests/test_jkn_host.py shows on the same parameters
+and inputs that a defect of one hidden unit or one input column moves out and alpha by at least 1e-4."""
 import os
 import threading
 
@@ -25,25 +34,33 @@ GOLD = os.path.join(os.path.dirname(__file__), "golden")
 TOL = 1e-5
 
 
-def _inputs(N, C, L, dev, seed, scale=1.0):
+def _inputs(N, C, L, dev, seed, scale=1.0, poison=False):
     """L separate [N, C] tensors of N(0, 1) values: one from `alloc_padded`, one a column slice of a wider tensor (its
-    leading dimension is not its width), one 4 bytes off every 16-byte boundary; then the same again."""
-    gen = torch.Generator().manual_seed(seed)
+    leading dimension is not its width), one 4 bytes off every 16-byte boundary; then the same again.  `poison`: each is the
+    first N rows of a buffer with three more, and whatever surrounds the values -- those rows, the other columns of the wide
+    tensor -- is NaN, so that a read outside an input shows in the result (the padding columns of `alloc_padded` stay
+    zero: that is its contract)."""
+    vs, G = R.jk_values(N, C, L, seed, scale)
+    nan = float("nan")
     xs = []
-    for t in range(L):
-        v = (torch.randn(N, C, generator=gen) * scale).to(dev)
+    for t, v in enumerate(vs):
         if t % 3 == 0:
-            x = alloc_padded(N, C, dev)
+            if poison:
+                buf = alloc_padded(N + 3, C, dev)
+                buf[N:] = nan
+                x = buf[:N]
+            else:
+                x = alloc_padded(N, C, dev)
         elif t % 3 == 1:
-            x = torch.zeros(N, C + 7, device=dev)[:, 3:3 + C]
+            x = torch.full((N + 3, C + 7), nan, device=dev)[:N, 3:3 + C] if poison else torch.zeros(N, C + 7, device=dev)[:, 3:3 + C]
             assert N <= 1 or x.stride(0) == C + 7
         else:
-            x = torch.empty(N * C + 1, device=dev)[1:].view(N, C)
+            x = (torch.full(((N + 3) * C + 1,), nan, device=dev)[1:1 + N * C] if poison
+                 else torch.empty(N * C + 1, device=dev)[1:]).view(N, C)
             assert N == 0 or x.data_ptr() % 16 == 4
-        x.copy_(v)
+        x.copy_(v.to(dev))
         xs.append(x.requires_grad_())
-    G = torch.randn(N, C, generator=gen).to(dev)
-    return xs, G
+    return xs, G.to(dev)
 
 
 def _module(C, L, dev, seed=0, chunk_rows=jk.DEFAULT_CHUNK_ROWS):
@@ -92,6 +109,105 @@ def test_kernels_against_float64(cuda, N, C, L):
     assert got[0].shape == (N, C)
     assert all(v <= TOL for v in errs.values()), errs
     assert float(got[1]["att.bias"].abs().max()) == 0.0                  # exactly zero, not rounding noise
+
+
+ULP = 2.0 ** -23                   # of a float32 in [1, 2)
+
+
+def _check_alpha(agg, xs, want_out, want_alpha, relu=False, paths=(True, False)):
+    """`jk.lstm_forward` itself, on the fused kernel and on the composed pieces (in chunks of 96 rows where there are more):
+    `out` and `alpha` -- which the whole backward is built on -- against float64, the rows of alpha summing to 1 within 4
+    ulps (alpha_t = e_t / fl(sum e): L - 1 roundings in the sum and one per quotient, half an ulp each, L <= 8).  Returns the
+    worst (out, alpha) error."""
+    N, L = xs[0].size(0), len(xs)
+    params = [p.detach() for p in agg._lstm_parameters()]
+    worst = [0.0, 0.0]
+    for fused in paths:
+        out, alpha = jk.lstm_forward([x.detach() for x in xs], params, agg.att.weight.detach().reshape(-1),
+                                     agg.att.bias.detach(), relu, fused, 96 if N > 96 else jk.DEFAULT_CHUNK_ROWS)
+        torch.cuda.synchronize()
+        assert out.shape == want_out.shape and alpha.shape == (N, L)
+        assert bool(torch.isfinite(out).all()) and bool(torch.isfinite(alpha).all()), fused
+        e_out, e_alpha = rel_err(out, want_out), rel_err(alpha, want_alpha)
+        off_one = float((alpha.double().sum(1) - 1).abs().max())
+        print(f"jk lstm_forward N={N} C={xs[0].size(1)} L={L} relu={relu} fused={fused}: out {e_out:.2e}, alpha {e_alpha:.2e}, "
+              f"|sum alpha - 1| {off_one / ULP:.2f} ulp")
+        assert e_out <= TOL and e_alpha <= TOL, (fused, e_out, e_alpha)
+        assert off_one <= 4 * ULP, (fused, off_one)
+        worst = [max(worst[0], e_out), max(worst[1], e_alpha)]
+    return worst
+
+
+def _finite(res):
+    return all(bool(torch.isfinite(t).all()) for t in _flat(res))
+
+
+@pytest.mark.parametrize("C,L", SHAPES)
+@pytest.mark.parametrize("N", [1, 31, 33, 257])
+def test_alpha_against_float64_on_both_paths(cuda, N, C, L):
+    agg = _module(C, L, cuda, seed=C + L)
+    xs, _ = _inputs(N, C, L, cuda, 1000 + N + C + L)
+    _check_alpha(agg, xs, *R.jk_truth(xs, agg.state_dict(), with_alpha=True))
+
+
+# Every leaf of the fused forward's dispatch (the table and its reasons: `_jkn_ref.LEAF_SHAPES`), each at one node, at a
+# partly filled wave and at one node past a full workgroup: 128 nodes on 4 waves, 64 on 2.
+LEAF_CASES = [(N, C, L, waves) for C, L, waves in R.LEAF_SHAPES for N in ((1, 33, 129) if waves == 4 else (1, 33, 65))]
+
+
+@pytest.mark.parametrize("N,C,L,waves", LEAF_CASES)
+def test_every_leaf_of_the_fused_forward_against_float64(cuda, N, C, L, waves):
+    """out, alpha and every gradient at each k_jk_fwd<NHB> and workgroup shape, the inputs surrounded by NaN."""
+    H = (L * C) // 2
+    module_seed, input_seed = R.leaf_seeds(N, C, L)
+    agg = _module(C, L, cuda, seed=module_seed, chunk_rows=96)
+    assert agg.lstm.hidden_size == H and agg.takes_fused_path()
+    # the library answers whether the kernel takes H, not on how many waves: `_jkn_ref.fwd_waves` restates the launcher's
+    # arithmetic (139 is the last width on 4 waves, 140 the first on 2) and has to agree with the answer it does give
+    assert R.fwd_waves(H) == waves and jk.fused_forward_takes(H)
+    xs, G = _inputs(N, C, L, cuda, input_seed, poison=True)
+    got = _run(agg, xs, G)
+    *want, want_alpha = R.jk_truth(xs, agg.state_dict(), G, with_alpha=True)
+    errs = _errors(got, want)
+    print(f"jk leaf N={N} C={C} L={L} H={H} NHB={(H + 31) // 32} waves={waves}: "
+          + ", ".join(f"{k} {v:.2e}" for k, v in errs.items()) + f", worst gradient {max(v for k, v in errs.items() if k != 'out'):.2e}")
+    assert got[0].shape == (N, C) and _finite(got)
+    assert all(v <= TOL for v in errs.values()), errs
+    assert float(got[1]["att.bias"].abs().max()) == 0.0
+    _check_alpha(agg, xs, want[0], want_alpha)
+
+
+@pytest.mark.parametrize("N,C,L", [(65, 64, 8), (129, 97, 2)])
+def test_relu_epilogue_on_the_new_leaves(cuda, N, C, L):
+    module_seed, input_seed = R.leaf_seeds(N, C, L)
+    agg = _module(C, L, cuda, seed=module_seed, chunk_rows=96)
+    assert agg.takes_fused_path()
+    xs, G = _inputs(N, C, L, cuda, input_seed, poison=True)
+    got = _run(agg, xs, G, relu=True)
+    *want, want_alpha = R.jk_truth(xs, agg.state_dict(), G, relu=True, with_alpha=True)
+    errs = _errors(got, want)
+    print(f"jk leaf relu N={N} C={C} L={L}: " + ", ".join(f"{k} {v:.2e}" for k, v in errs.items()))
+    assert _finite(got) and all(v <= TOL for v in errs.values()), errs
+    assert float(got[0].min()) >= 0.0 and bool((got[0] == 0).any())
+    _check_alpha(agg, xs, want[0], want_alpha, relu=True)
+
+
+@pytest.mark.parametrize("N", [33, 129])
+def test_a_width_beyond_the_fused_kernel_takes_the_composed_path(cuda, N):
+    """H = 257: nine blocks of hidden units.  The switch stays on; the module goes to the composed pieces on its own."""
+    C, L = 257, 2
+    module_seed, input_seed = R.leaf_seeds(N, C, L)
+    agg = _module(C, L, cuda, seed=module_seed, chunk_rows=96)
+    assert agg.lstm.hidden_size == 257 and R.fwd_waves(257) == 0
+    assert not jk.fused_forward_takes(257) and not agg.takes_fused_path()
+    xs, G = _inputs(N, C, L, cuda, input_seed, poison=True)
+    got = _run(agg, xs, G)
+    *want, want_alpha = R.jk_truth(xs, agg.state_dict(), G, with_alpha=True)
+    errs = _errors(got, want)
+    print(f"jk composed N={N} C={C} L={L} H=257: " + ", ".join(f"{k} {v:.2e}" for k, v in errs.items()))
+    assert _finite(got) and all(v <= TOL for v in errs.values()), errs
+    assert float(got[1]["att.bias"].abs().max()) == 0.0
+    _check_alpha(agg, xs, want[0], want_alpha, paths=(False,))
 
 
 def test_inputs_scaled_by_four_against_float64(cuda):

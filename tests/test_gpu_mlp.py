@@ -5,7 +5,9 @@ The kernels are held to a float64 restatement (tests/_mlp_ref.py) at the project
 G ~ N(0, 1); p in {0, 0.3, 0.7}) sits at 1.0e-7 .. 8.9e-7 from float64 over C, dZ, db, dW and dc at (N, k, n) = (1025, 256,
 128), (333, 515, 33), (129, 63, 219), (1025, 257, 219), (33, 515, 300), (1025, 515, 3), (1025, 1, 32), (31, 256, 300),
 (1, 257, 33), (1025, 128, 129), (4100, 515, 3) and (8300, 256, 33) -- the worst is dW at (333, 515, 33) -- so the bar leaves more than ten-fold room at every
-shape used here and no operand is rescaled.
+shape used here and no operand is rescaled.  On ROUNDED_CASES (the forward's tile counts that are rounded up to a leaf,
+operands surrounded by NaN) the kernels on an MI355X stay within C 4.0e-7, dZ 3.2e-7, db 3.2e-7, dW 4.3e-7, and a column's
+bits do not depend on the leaf that serves it (torch.equal, no tolerance).
 The dropout mask is held to tests/_dropout_hash.py bit for bit.  The model is held to the reference's MLP restated from
 torch's Linear / SELU / Dropout (tests/_mlp_ref.MLPRef) in float64."""
 import math
@@ -91,6 +93,82 @@ def test_kernels_against_float64_without_dropout(cuda, N, k, n, ldz_extra, strid
     only_z = mlp.act_linear_backward(Z, b, W, G, want_w=False)
     assert only_w[0] is None and only_w[1] is None and only_z[2] is None
     assert torch.equal(only_w[2], dW) and torch.equal(only_z[0], dZ) and torch.equal(only_z[1], db)
+
+
+# The forward serves a group of nt = ceil(ng / 32) tiles of result columns on the next leaf of NT in {1, 2, 4, 8}.  CASES
+# runs every leaf, and nt = 3 only in dZ (the second 128-wide group of n = 219).  Here the forward's rounding nt = 3 on
+# NT = 4 (n = 65, 96: the fourth tile is all padding), and a full group followed by a group of one column (256 | 257).
+# k in {33, 63} and N in {33, 129}: one and two chunks of k, one and two tiles of rows, a tail in each.  Layout of CASES.
+ROUNDED_CASES = [
+    (33, 33, 65, 0, False, True), (129, 63, 96, 3, True, False), (129, 63, 65, 0, False, False), (33, 33, 96, 1, False, True),
+    (129, 33, 256, 0, False, True), (33, 63, 257, 2, True, True), (129, 63, 257, 0, False, False),
+]
+
+
+def _in_nan(rows, cols, values, dev, col0=0, more_cols=0):
+    """`values` [rows, cols] as a slice of a buffer with two more rows that is NaN everywhere else."""
+    buf = torch.full((rows + 2, col0 + cols + more_cols), float("nan"), device=dev)
+    view = buf[:rows, col0:col0 + cols]
+    view.copy_(values)
+    return view
+
+
+@pytest.mark.parametrize("N,k,n,ldz_extra,strided,with_c", ROUNDED_CASES)
+def test_rounded_up_leaves_against_float64_among_nan(cuda, N, k, n, ldz_extra, strided, with_c):
+    """The checks of `test_kernels_against_float64_without_dropout` with every operand surrounded by NaN: Zbuf's columns past
+    k and two rows past N, W's rows past n and columns past k, G's surroundings.  No result may hold one."""
+    Z, b, W, c, G = _on(cuda, N, k, n, 1000 + N + k + n, ldz_extra)
+    Z = _in_nan(N, k, Z, cuda, more_cols=ldz_extra)
+    W = _in_nan(n, k, W, cuda, more_cols=3)
+    assert (Z.stride(0) == k + ldz_extra or N <= 1) and W.stride(0) == k + 3
+    c = c if with_c else None
+    out = None
+    if strided:
+        wide = torch.full((N, n + 9), 7.0, device=cuda)
+        out = wide[:, 5:5 + n]
+        G = _in_nan(N, n, G, cuda, col0=3, more_cols=4)
+    else:
+        G = _in_nan(N, n, G, cuda)
+    C = mlp.act_linear_forward(Z, b, W, c, out=out)
+    dZ, db, dW = mlp.act_linear_backward(Z, b, W, G)
+    torch.cuda.synchronize()
+    assert C.shape == (N, n) and dZ.shape == (N, k) and db.shape == (k,) and dW.shape == (n, k)
+    if strided:
+        assert bool((wide[:, :5] == 7.0).all()) and bool((wide[:, 5 + n:] == 7.0).all())   # nothing outside the n columns
+    assert all(bool(torch.isfinite(t).all()) for t in (C, dZ, db, dW))
+    tC, tZ, tb, tW, _ = R.fused_truth(Z, b, W, c, G)
+    errs = {"C": rel_err(C, tC), "dZ": rel_err(dZ, tZ), "db": rel_err(db, tb), "dW": rel_err(dW, tW)}
+    print(f"mlp kernels, rounded-up leaves, N={N} k={k} n={n}: " + ", ".join(f"{key} {v:.2e}" for key, v in errs.items()))
+    assert all(v <= TOL for v in errs.values()), errs
+    only_w = mlp.act_linear_backward(Z, b, W, G, want_z=False)
+    only_z = mlp.act_linear_backward(Z, b, W, G, want_w=False)
+    assert torch.equal(only_w[2], dW) and torch.equal(only_z[0], dZ) and torch.equal(only_z[1], db)
+
+
+_FULL_GROUP = {}
+
+
+def _full_group(dev):
+    """Operands with n = 256 -- eight full tiles on NT = 8, dW on k_mlp_grad_w<2> -- and their C and dW, computed once."""
+    if not _FULL_GROUP:
+        Z, b, W, c, G = _on(dev, 129, 63, 256, 4242)
+        _FULL_GROUP["v"] = (Z, b, W, c, G, mlp.act_linear_forward(Z, b, W, c), mlp.act_linear_backward(Z, b, W, G, want_z=False)[2])
+    return _FULL_GROUP["v"]
+
+
+@pytest.mark.parametrize("n1", [65, 96, 129, 192])
+def test_bits_of_a_column_do_not_depend_on_the_leaf_that_serves_it(cuda, n1):
+    """By construction, no tolerance.  An element of C is accumulated over k in the same order whichever NT serves its tile
+    (`acc[t]` of k_mlp_fwd depends on its own column only, and the output bias is added to the finished sum), so the forward
+    on W[:n1], c[:n1] -- NT = 4 with a padding tile, or NT = 8 with up to three -- gives the first n1 columns of the forward
+    on all 256.  The row slices of dW are set by N and k alone (`grad_w_split`) and k_mlp_reduce_w adds them in slice order
+    under either TW (two slices here), so the rows dW[:n1] are those of the run with G[:, :n1].  A difference means a leaf
+    sums in another order or reads its padding."""
+    Z, b, W, c, G, C, dW = _full_group(cuda)
+    G1 = G[:, :n1]
+    assert G1.stride(0) == 256
+    assert torch.equal(mlp.act_linear_forward(Z, b, W[:n1], c[:n1]), C[:, :n1])
+    assert torch.equal(mlp.act_linear_backward(Z, b, W[:n1], G1, want_z=False)[2], dW[:n1])
 
 
 def _seed_tensor(value, dev):

@@ -1,6 +1,7 @@
 """`pytextgcn_amd.JumpingKnowledgeNetwork`, `pytextgcn_amd.jk.JumpingKnowledge` and the `tgcn_jk_*` entry points as far
 as a host without a GPU can see them: the public surface against the reference's (textgcn/lib/models.py:55-81), state_dict
-exchange, pickling, the argument checks.  The arithmetic is tested on the GPU (tests/test_gpu_jkn.py)."""
+exchange, pickling, the argument checks.  The arithmetic is tested on the GPU (tests/test_gpu_jkn.py); here, in float64 on
+the CPU, only that the inputs of its leaf tests let the bar see a defect of one hidden unit."""
 import ctypes
 import inspect
 import io
@@ -13,6 +14,7 @@ from torch import nn
 import pytextgcn_amd as pkg
 from pytextgcn_amd import _lib, jk
 
+import _jkn_ref as R
 from _jkn_ref import JKNRef, JKRef
 
 
@@ -116,6 +118,39 @@ def test_cat_and_max_are_the_torch_expressions():
     assert torch.equal(jk.JumpingKnowledge("cat")(xs), torch.cat(xs, dim=-1))
     assert torch.equal(jk.JumpingKnowledge("max")(xs), torch.stack(xs, dim=-1).max(dim=-1)[0])
     assert not list(jk.JumpingKnowledge("max").parameters())
+
+
+def _defects(C, H):
+    """Three one-unit defects of a fused LSTM kernel, simulated in the parameters: (A) the last hidden unit of the reverse
+    direction never reaches the score, (B) the last input column is dropped from the forward direction's input product,
+    (C) the last recurrent column is dropped in the reverse direction."""
+    return {"A": ("att.weight", (0, 2 * H - 1)), "B": ("lstm.weight_ih_l0", (slice(None), C - 1)),
+            "C": ("lstm.weight_hh_l0_reverse", (slice(None), H - 1))}
+
+
+@pytest.mark.parametrize("C,L,waves", R.LEAF_SHAPES)
+def test_the_bar_sees_a_one_unit_defect_on_the_leaf_tests_inputs(C, L, waves):
+    """With default initialisation alpha stays within about +-0.05 of 1 / L, so `out` might hide an error of the LSTM.  It
+    does not on the inputs of tests/test_gpu_jkn.py's leaf tests: in float64, at N = 33, each defect of `_defects` moves
+    `out` and `alpha` by at least 10 x the bar of 1e-5.  A condition on the chosen parameters and inputs (`leaf_seeds`),
+    not a tolerance on the kernel: a seed that misses it is changed, the factor is not."""
+    N, H, TOL = 33, (L * C) // 2, 1e-5
+    assert R.fwd_waves(H) == waves and (H + 31) // 32 <= 8
+    module_seed, input_seed = R.leaf_seeds(N, C, L)
+    torch.manual_seed(module_seed)
+    state = jk.JumpingKnowledge("lstm", channels=C, num_layers=L).state_dict()
+    xs, _ = R.jk_values(N, C, L, input_seed)
+    out, alpha = R.jk_truth(xs, state, with_alpha=True)
+    assert float((alpha.sum(1) - 1).abs().max()) <= 1e-12
+    moved = {}
+    for tag, (key, where) in _defects(C, H).items():
+        broken = {k: v.clone() for k, v in state.items()}
+        assert float(broken[key][where].abs().min()) > 0.0
+        broken[key][where] = 0.0
+        o, a = R.jk_truth(xs, broken, with_alpha=True)
+        moved[tag] = (R.rel_err(o, out), R.rel_err(a, alpha))
+    print(f"jk defects C={C} L={L} H={H}: " + ", ".join(f"({k}) out {o:.1e} alpha {a:.1e}" for k, (o, a) in moved.items()))
+    assert all(o >= 10 * TOL and a >= 10 * TOL for o, a in moved.values()), moved
 
 
 def test_entry_points_check_their_arguments_without_a_gpu():
