@@ -1,0 +1,147 @@
+// What the fused-activation products (embed.hip, mlp.hip) and the other matrix-core kernels of the model layers (jk.hip,
+// hier.hip's entry points) share: the accumulator map of v_mfma_f32_32x32x2_f32, SELU, the dropout decision of one
+// element, the argument checks of the entry points, the cut of a reduction into slices and the sum over the slices.
+// Everything here is inline, a template or in an unnamed namespace: a translation unit holds a copy of what it uses.
+#pragma once
+
+#include <algorithm>
+#include <type_traits>
+
+#include "common.h"
+#include "drop_hash.h"
+
+namespace tgcn {
+
+// v_mfma_f32_32x32x2_f32 (exact fp32), the fragment maps as in dense.hip: lane l feeds A[l & 31][l >> 5] and
+// B[l >> 5][l & 31]; register r of lane l is C[acc_row(r, l >> 5)][l & 31].
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+__device__ __forceinline__ int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+
+// torch's constants (aten/src/ATen/native/Activation.cpp: selu)
+constexpr float kSeluScale = 1.0507009873554805f;
+constexpr float kSeluNeg = static_cast<float>(1.0507009873554805 * 1.6732632423543772);   // scale * alpha
+
+__device__ __forceinline__ float selu_f(float x) { return x > 0.f ? kSeluScale * x : kSeluNeg * expm1f(x); }
+__device__ __forceinline__ float selu_grad_f(float x) { return x > 0.f ? kSeluScale : kSeluNeg * expf(x); }
+
+// The dropout of a row-indexed activation: keep(i, col) is the decision of tgcn_gemm_*_dropout (drop_hash.h) for mask row
+// i + row0 and column col.
+struct RowDrop {
+    const uint64_t *seed;  // device pointer (read by the kernels: safe under HIP-graph capture)
+    uint32_t thresh;       // keep iff hash >= thresh
+    float scale;           // 1 / (1 - p)
+    int64_t row0;          // row i is mask row i + row0
+};
+
+template <bool DROP>
+__device__ __forceinline__ uint32_t row_key(const RowDrop &d, int64_t i) {
+    if constexpr (DROP) {
+        const uint64_t seed = *d.seed;
+        return drop_row_key(static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), i + d.row0);
+    }
+    return 0u;
+}
+
+// s * keep * selu(z); `key` is the row's key, `col_term` the column's term of the hash
+template <bool DROP>
+__device__ __forceinline__ float act(float z, uint32_t key, uint32_t col_term, const RowDrop &d) {
+    const float a = selu_f(z);
+    if constexpr (DROP) return drop_hash_keep(key, col_term, d.thresh) ? a * d.scale : 0.f;
+    return a;
+}
+
+inline int make_row_drop(const char *fn, double p, const uint64_t *seed, int64_t mask_row0, RowDrop &d, bool &on) {
+    if (!(p >= 0.0 && p < 1.0)) {
+        set_error("%s: p must be in [0, 1) (p=%g)", fn, p);
+        return TGCN_E_INVALID;
+    }
+    if (mask_row0 < 0) {
+        set_error("%s: mask_row0 must be >= 0 (%lld)", fn, (long long)mask_row0);
+        return TGCN_E_INVALID;
+    }
+    on = p > 0.0 && seed != nullptr;
+    d.seed = seed;
+    d.thresh = on ? drop_threshold(p) : 0u;
+    d.scale = on ? static_cast<float>(1.0 / (1.0 - p)) : 1.f;
+    d.row0 = mask_row0;
+    return TGCN_OK;
+}
+
+// The argument checks of the entry points, used under TGCN_CHECK.
+inline int check_ld(const char *fn, const char *name, int64_t ld, int64_t extent) {
+    if (ld < extent) {
+        set_error("%s: %s (%lld) is smaller than the extent %lld", fn, name, (long long)ld, (long long)extent);
+        return TGCN_E_INVALID;
+    }
+    return TGCN_OK;
+}
+
+inline int check_ptr(const char *fn, const char *name, const void *ptr) {
+    if (!ptr) {
+        set_error("%s: %s is NULL", fn, name);
+        return TGCN_E_INVALID;
+    }
+    return TGCN_OK;
+}
+
+// `k`: how the entry point's signature spells the activation's width ("K" or "k")
+inline int check_sizes(const char *fn, const char *k, int64_t N, int K, int n) {
+    if (N < 0 || K <= 0 || n <= 0) {
+        set_error("%s: need N >= 0, %s >= 1 and n >= 1 (N=%lld, %s=%d, n=%d)", fn, k, (long long)N, k, K, n);
+        return TGCN_E_INVALID;
+    }
+    return TGCN_OK;
+}
+
+// f(std::integral_constant<int, T>) for the first T of the ascending ladder TS... with t <= T (the last one when there is
+// none): how a launcher picks the instantiation for a run-time tile count
+template <int T, int... TS, class F>
+inline void with_tiles(int t, F &&f) {
+    if constexpr (sizeof...(TS) == 0) {
+        f(std::integral_constant<int, T>{});
+    } else {
+        if (t <= T) f(std::integral_constant<int, T>{});
+        else with_tiles<TS...>(t, f);
+    }
+}
+
+// A reduction over N rows for a result of ceil(K / 32) tiles, cut into slices of whole chunks of kWChunk rows: about
+// `target_workgroups` workgroups in all, at most 256 slices.  The slices' partial sums go to a workspace and
+// k_reduce_slices adds them in slice order: no atomics, the same bits every run.
+constexpr int kWChunk = 128;   // rows per staged tile
+
+inline void grad_w_split(int64_t N, int K, int target_workgroups, int64_t &slices, int64_t &chunks_per_slice) {
+    const int64_t chunks = std::max<int64_t>(1, (N + kWChunk - 1) / kWChunk);
+    const int64_t ktiles = (int64_t(K) + 31) / 32;
+    const int64_t want = std::min<int64_t>(256, std::max<int64_t>(1, target_workgroups / ktiles));
+    chunks_per_slice = (chunks + want - 1) / want;
+    slices = (chunks + chunks_per_slice - 1) / chunks_per_slice;
+}
+
+namespace {   // (a kernel in a header: every translation unit that launches it has its own; as a template, no other has one)
+
+// out[r, j] = sum over the slices q, in order, of part[q * slice_stride + r * row_stride + j]
+template <class T>
+__global__ __launch_bounds__(256) void k_reduce_slices(const T *__restrict__ part, int slices, int64_t slice_stride,
+                                                       int row_stride, int rows, int cols, T *__restrict__ out, int64_t ld) {
+    const int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (e >= int64_t(rows) * cols) return;
+    const int r = static_cast<int>(e / cols), j = static_cast<int>(e % cols);
+    const T *p = part + int64_t(r) * row_stride + j;
+    T s = 0;
+    for (int q = 0; q < slices; ++q) s += p[q * slice_stride];
+    out[int64_t(r) * ld + j] = s;
+}
+
+template <class T>
+void launch_reduce_slices(const T *part, int64_t slices, int64_t slice_stride, int row_stride, int rows, int cols, T *out,
+                          int64_t ld, hipStream_t s) {
+    const unsigned grid = static_cast<unsigned>((int64_t(rows) * cols + 255) / 256);
+    hipLaunchKernelGGL(k_reduce_slices<T>, dim3(grid), dim3(256), 0, s, part, static_cast<int>(slices), slice_stride,
+                       row_stride, rows, cols, out, ld);
+}
+
+}  // namespace
+
+}  // namespace tgcn

@@ -23,7 +23,7 @@
 // A class id outside [0, Fh) selects nothing (the rule of tgcn_rows_gather: skipped on the device, never read through).
 #include <algorithm>
 
-#include "common.h"
+#include "fused_act.h"
 
 namespace tgcn {
 namespace {
@@ -222,17 +222,6 @@ int check_hier(const char *fn, int64_t N, int F, int Fh, int64_t h_row0, int for
     return TGCN_OK;
 }
 
-#define TGCN_HIER_LD(name, ld, extent)                                                                      \
-    if ((ld) < (extent)) {                                                                                  \
-        set_error("%s: " name " (%lld) is smaller than the extent %lld", fn, (long long)(ld), (long long)(extent)); \
-        return TGCN_E_INVALID;                                                                              \
-    }
-#define TGCN_HIER_PTR(name, ptr)                             \
-    if (!(ptr)) {                                            \
-        set_error("%s: " name " is NULL", fn);               \
-        return TGCN_E_INVALID;                               \
-    }
-
 unsigned row_blocks(int64_t n) { return static_cast<unsigned>((n + kRowBlock - 1) / kRowBlock); }
 
 }  // namespace
@@ -247,15 +236,15 @@ int tgcn_hier_xw(const float *W, int64_t ldw, int form, const int32_t *cls, cons
     using namespace tgcn;
     const char *fn = "tgcn_hier_xw";
     TGCN_CHECK(check_hier(fn, N, F, Fh, h_row0, form));
-    TGCN_HIER_LD("ldw", ldw, F);
-    TGCN_HIER_LD("ldc", ldc, F);
-    if (form == TGCN_HIER_DENSE) TGCN_HIER_LD("ldh", ldh, Fh);
+    TGCN_CHECK(check_ld(fn, "ldw", ldw, F));
+    TGCN_CHECK(check_ld(fn, "ldc", ldc, F));
+    if (form == TGCN_HIER_DENSE) TGCN_CHECK(check_ld(fn, "ldh", ldh, Fh));
     if (N == 0) return TGCN_OK;                // (an empty tensor's pointer may be NULL)
-    TGCN_HIER_PTR("W", W);
-    TGCN_HIER_PTR("C", C);
+    TGCN_CHECK(check_ptr(fn, "W", W));
+    TGCN_CHECK(check_ptr(fn, "C", C));
     if (h_row0 < N) {
-        if (form == TGCN_HIER_ONEHOT) TGCN_HIER_PTR("cls", cls);
-        if (form == TGCN_HIER_DENSE) TGCN_HIER_PTR("Hd", Hd);
+        if (form == TGCN_HIER_ONEHOT) TGCN_CHECK(check_ptr(fn, "cls", cls));
+        if (form == TGCN_HIER_DENSE) TGCN_CHECK(check_ptr(fn, "Hd", Hd));
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const float *Wh = W + N * ldw;
@@ -292,15 +281,15 @@ int tgcn_hier_xw_grad(const float *G, int64_t ldg, int form, const int32_t *cls,
     using namespace tgcn;
     const char *fn = "tgcn_hier_xw_grad";
     TGCN_CHECK(check_hier(fn, N, F, Fh, h_row0, form));
-    TGCN_HIER_LD("ldg", ldg, F);
-    TGCN_HIER_LD("lddw", lddw, F);
-    TGCN_HIER_PTR("dW", dW);
-    if (N > 0) TGCN_HIER_PTR("G", G);
+    TGCN_CHECK(check_ld(fn, "ldg", ldg, F));
+    TGCN_CHECK(check_ld(fn, "lddw", lddw, F));
+    TGCN_CHECK(check_ptr(fn, "dW", dW));
+    if (N > 0) TGCN_CHECK(check_ptr(fn, "G", G));
     const int64_t n_doc = N - h_row0;
     const bool sums = form == TGCN_HIER_ONEHOT;            // DENSE: dW[N:] is the caller's tgcn_gemm_tn
     const size_t need = sums ? class_sum_bytes(n_doc, F, Fh) : 0;
     if (sums && n_doc > 0) {
-        TGCN_HIER_PTR("cls", cls);
+        TGCN_CHECK(check_ptr(fn, "cls", cls));
         if (!workspace || workspace_bytes < need) {        // before anything is enqueued
             set_error("%s: workspace of %zu bytes, tgcn_hier_xw_grad_workspace_bytes() asks for %zu", fn, workspace_bytes, need);
             return TGCN_E_INVALID;

@@ -5,7 +5,7 @@
 // torch's parameter layout throughout: W_ih [4 H, C], W_hh [4 H, H], gate order i, f, g, o.
 //
 //   tgcn_jk_lstm_forward   the whole step as ONE kernel: a wave owns 32 nodes and carries them through both directions and
-//                          all L steps on v_mfma_f32_32x32x2_f32 (exact fp32; fragment maps as in dense.hip / embed.hip).
+//                          all L steps on v_mfma_f32_32x32x2_f32 (exact fp32; fragment maps: fused_act.h).
 //                          Only out [N, C] and alpha [N, L] reach memory: no gate, cell or hidden value does.
 //   tgcn_jk_cell, tgcn_jk_attention                          the same arithmetic as pointwise pieces around the library's
 //   tgcn_jk_attention_grad, tgcn_jk_cell_grad,               tall-skinny products: the composed forward and the backward by
@@ -14,12 +14,10 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "common.h"
+#include "fused_act.h"
 
 namespace tgcn {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct JkInputs {
     const float *x[TGCN_JK_MAX_LAYERS];
@@ -32,8 +30,6 @@ struct JkDir {
 
 // the accurate forms: expf / tanhf, no fast-math intrinsics (the bar is 1e-5 against float64 through L recurrent steps)
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
-
-__device__ __forceinline__ int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 // f(integral_constant<0>) ... f(integral_constant<N - 1>): a loop whose index is a constant in every copy of the body (the
 // cell state is a register array indexed by it; an `unroll` pragma the compiler may decline would put it in scratch)
@@ -321,18 +317,7 @@ __global__ __launch_bounds__(256) void k_jk_input_grad(float *__restrict__ dx, i
     dx[row * lddx + col] = alpha[row * lda] * g + T[row * ldt + col];
 }
 
-#define TGCN_JK_LD(name, ld, extent)                                                                        \
-    if ((ld) < (extent)) {                                                                                  \
-        set_error("%s: " name " (%lld) is smaller than the extent %lld", fn, (long long)(ld), (long long)(extent)); \
-        return TGCN_E_INVALID;                                                                              \
-    }
-#define TGCN_JK_PTR(name, ptr)                               \
-    if (!(ptr)) {                                            \
-        set_error("%s: " name " is NULL", fn);               \
-        return TGCN_E_INVALID;                               \
-    }
-
-int check_sizes(const char *fn, int64_t R, int a, int b) {
+int check_widths(const char *fn, int64_t R, int a, int b) {
     if (R < 0 || a <= 0 || b <= 0) {
         set_error("%s: need a row count >= 0 and widths >= 1 (rows=%lld, widths %d, %d)", fn, (long long)R, a, b);
         return TGCN_E_INVALID;
@@ -346,15 +331,15 @@ int gather_inputs(const char *fn, const float *const *xs, const int64_t *ldxs, i
         set_error("%s: %d layers; 1 .. TGCN_JK_MAX_LAYERS = %d are taken", fn, L, TGCN_JK_MAX_LAYERS);
         return TGCN_E_INVALID;
     }
-    TGCN_JK_PTR("xs", xs);
-    TGCN_JK_PTR("ldxs", ldxs);
+    TGCN_CHECK(check_ptr(fn, "xs", xs));
+    TGCN_CHECK(check_ptr(fn, "ldxs", ldxs));
     for (int t = 0; t < TGCN_JK_MAX_LAYERS; ++t) {
         in.x[t] = nullptr;
         in.ld[t] = 0;
     }
     for (int t = 0; t < L; ++t) {
-        TGCN_JK_LD("ldxs[t]", ldxs[t], C);
-        if (R > 0) TGCN_JK_PTR("xs[t]", xs[t]);
+        TGCN_CHECK(check_ld(fn, "ldxs[t]", ldxs[t], C));
+        if (R > 0) TGCN_CHECK(check_ptr(fn, "xs[t]", xs[t]));
         in.x[t] = xs[t];
         in.ld[t] = ldxs[t];
     }
@@ -375,13 +360,13 @@ int tgcn_jk_lstm_forward(const float *const *xs, const int64_t *ldxs, int L, int
                          float *out, int64_t ldo, float *alpha, int64_t lda, int relu, tgcn_stream stream) {
     using namespace tgcn;
     const char *fn = "tgcn_jk_lstm_forward";
-    TGCN_CHECK(check_sizes(fn, N, C, H));
+    TGCN_CHECK(check_widths(fn, N, C, H));
     JkInputs in;
     TGCN_CHECK(gather_inputs(fn, xs, ldxs, L, N, C, in));
-    TGCN_JK_LD("ldwi", ldwi, C);
-    TGCN_JK_LD("ldwh", ldwh, H);
-    TGCN_JK_LD("ldo", ldo, C);
-    TGCN_JK_LD("lda", lda, L);
+    TGCN_CHECK(check_ld(fn, "ldwi", ldwi, C));
+    TGCN_CHECK(check_ld(fn, "ldwh", ldwh, H));
+    TGCN_CHECK(check_ld(fn, "ldo", ldo, C));
+    TGCN_CHECK(check_ld(fn, "lda", lda, L));
     const int waves = fwd_waves(H);
     if (waves == 0) {
         set_error("%s: hidden width %d is beyond the fused kernel (at most %d); run the composed pieces", fn, H,
@@ -389,12 +374,12 @@ int tgcn_jk_lstm_forward(const float *const *xs, const int64_t *ldxs, int L, int
         return TGCN_E_INVALID;
     }
     if (N == 0) return TGCN_OK;
-    TGCN_JK_PTR("lstm", lstm);
-    for (int q = 0; q < 8; ++q) TGCN_JK_PTR("lstm[q]", lstm[q]);
-    TGCN_JK_PTR("att_w", att_w);
-    TGCN_JK_PTR("att_b", att_b);
-    TGCN_JK_PTR("out", out);
-    TGCN_JK_PTR("alpha", alpha);
+    TGCN_CHECK(check_ptr(fn, "lstm", lstm));
+    for (int q = 0; q < 8; ++q) TGCN_CHECK(check_ptr(fn, "lstm[q]", lstm[q]));
+    TGCN_CHECK(check_ptr(fn, "att_w", att_w));
+    TGCN_CHECK(check_ptr(fn, "att_b", att_b));
+    TGCN_CHECK(check_ptr(fn, "out", out));
+    TGCN_CHECK(check_ptr(fn, "alpha", alpha));
     const JkDir d0{lstm[0], lstm[1], lstm[2], lstm[3]}, d1{lstm[4], lstm[5], lstm[6], lstm[7]};
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t lds = fwd_lds_bytes(H, waves);
@@ -426,20 +411,20 @@ int tgcn_jk_cell(const float *pre_x, int64_t ldpx, const float *pre_h, int64_t l
                  int64_t R, int H, tgcn_stream stream) {
     using namespace tgcn;
     const char *fn = "tgcn_jk_cell";
-    TGCN_CHECK(check_sizes(fn, R, H, H));
-    TGCN_JK_LD("ldpx", ldpx, 4 * int64_t(H));
-    TGCN_JK_LD("ldg", ldg, 4 * int64_t(H));
-    TGCN_JK_LD("ldc", ldc, H);
-    TGCN_JK_LD("ldh", ldh, H);
-    if (pre_h) TGCN_JK_LD("ldph", ldph, 4 * int64_t(H));
-    if (c_prev) TGCN_JK_LD("ldcp", ldcp, H);
+    TGCN_CHECK(check_widths(fn, R, H, H));
+    TGCN_CHECK(check_ld(fn, "ldpx", ldpx, 4 * int64_t(H)));
+    TGCN_CHECK(check_ld(fn, "ldg", ldg, 4 * int64_t(H)));
+    TGCN_CHECK(check_ld(fn, "ldc", ldc, H));
+    TGCN_CHECK(check_ld(fn, "ldh", ldh, H));
+    if (pre_h) TGCN_CHECK(check_ld(fn, "ldph", ldph, 4 * int64_t(H)));
+    if (c_prev) TGCN_CHECK(check_ld(fn, "ldcp", ldcp, H));
     if (R == 0) return TGCN_OK;
-    TGCN_JK_PTR("pre_x", pre_x);
-    TGCN_JK_PTR("b_ih", b_ih);
-    TGCN_JK_PTR("b_hh", b_hh);
-    TGCN_JK_PTR("gates", gates);
-    TGCN_JK_PTR("c", c);
-    TGCN_JK_PTR("h", h);
+    TGCN_CHECK(check_ptr(fn, "pre_x", pre_x));
+    TGCN_CHECK(check_ptr(fn, "b_ih", b_ih));
+    TGCN_CHECK(check_ptr(fn, "b_hh", b_hh));
+    TGCN_CHECK(check_ptr(fn, "gates", gates));
+    TGCN_CHECK(check_ptr(fn, "c", c));
+    TGCN_CHECK(check_ptr(fn, "h", h));
     hipLaunchKernelGGL(k_jk_cell, dim3(grid_of(R * H)), dim3(256), 0, static_cast<hipStream_t>(stream), pre_x, ldpx, pre_h,
                        ldph, b_ih, b_hh, c_prev, ldcp, gates, ldg, c, ldc, h, ldh, R, H);
     TGCN_HIP_CHECK(hipGetLastError());
@@ -451,23 +436,23 @@ int tgcn_jk_attention(const float *const *xs, const int64_t *ldxs, int L, int64_
                       int64_t ldo, float *alpha, int64_t lda, int relu, tgcn_stream stream) {
     using namespace tgcn;
     const char *fn = "tgcn_jk_attention";
-    TGCN_CHECK(check_sizes(fn, R, C, H));
+    TGCN_CHECK(check_widths(fn, R, C, H));
     JkInputs in;
     TGCN_CHECK(gather_inputs(fn, xs, ldxs, L, R, C, in));
-    TGCN_JK_LD("ldh", ldh, H);
-    TGCN_JK_LD("ldo", ldo, C);
-    TGCN_JK_LD("lda", lda, L);
+    TGCN_CHECK(check_ld(fn, "ldh", ldh, H));
+    TGCN_CHECK(check_ld(fn, "ldo", ldo, C));
+    TGCN_CHECK(check_ld(fn, "lda", lda, L));
     if (hstep < 0) {
         set_error("%s: hstep must be >= 0", fn);
         return TGCN_E_INVALID;
     }
     if (R == 0) return TGCN_OK;
-    TGCN_JK_PTR("h_fwd", h_fwd);
-    TGCN_JK_PTR("h_bwd", h_bwd);
-    TGCN_JK_PTR("att_w", att_w);
-    TGCN_JK_PTR("att_b", att_b);
-    TGCN_JK_PTR("out", out);
-    TGCN_JK_PTR("alpha", alpha);
+    TGCN_CHECK(check_ptr(fn, "h_fwd", h_fwd));
+    TGCN_CHECK(check_ptr(fn, "h_bwd", h_bwd));
+    TGCN_CHECK(check_ptr(fn, "att_w", att_w));
+    TGCN_CHECK(check_ptr(fn, "att_b", att_b));
+    TGCN_CHECK(check_ptr(fn, "out", out));
+    TGCN_CHECK(check_ptr(fn, "alpha", alpha));
     hipLaunchKernelGGL(k_jk_attention, dim3(static_cast<unsigned>((R + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        in, L, R, C, H, h_fwd, h_bwd, ldh, hstep, att_w, att_b, out, ldo, alpha, lda, relu);
     TGCN_HIP_CHECK(hipGetLastError());
@@ -479,17 +464,17 @@ int tgcn_jk_attention_grad(const float *const *xs, const int64_t *ldxs, int L, i
                            tgcn_stream stream) {
     using namespace tgcn;
     const char *fn = "tgcn_jk_attention_grad";
-    TGCN_CHECK(check_sizes(fn, R, C, C));
+    TGCN_CHECK(check_widths(fn, R, C, C));
     JkInputs in;
     TGCN_CHECK(gather_inputs(fn, xs, ldxs, L, R, C, in));
-    TGCN_JK_LD("ldg", ldg, C);
-    if (out) TGCN_JK_LD("ldo", ldo, C);
-    TGCN_JK_LD("lda", lda, L);
-    TGCN_JK_LD("ldds", ldds, L);
+    TGCN_CHECK(check_ld(fn, "ldg", ldg, C));
+    if (out) TGCN_CHECK(check_ld(fn, "ldo", ldo, C));
+    TGCN_CHECK(check_ld(fn, "lda", lda, L));
+    TGCN_CHECK(check_ld(fn, "ldds", ldds, L));
     if (R == 0) return TGCN_OK;
-    TGCN_JK_PTR("G", G);
-    TGCN_JK_PTR("alpha", alpha);
-    TGCN_JK_PTR("dscore", dscore);
+    TGCN_CHECK(check_ptr(fn, "G", G));
+    TGCN_CHECK(check_ptr(fn, "alpha", alpha));
+    TGCN_CHECK(check_ptr(fn, "dscore", dscore));
     hipLaunchKernelGGL(k_jk_attention_grad, dim3(static_cast<unsigned>((R + 3) / 4)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), in, L, R, C, G, ldg, out, ldo, alpha, lda, dscore, ldds);
     TGCN_HIP_CHECK(hipGetLastError());
@@ -501,21 +486,21 @@ int tgcn_jk_cell_grad(const float *gates, int64_t ldg, const float *c, int64_t l
                       int64_t lddc, int dc_zero, float *dgates, int64_t lddg, int64_t R, int H, tgcn_stream stream) {
     using namespace tgcn;
     const char *fn = "tgcn_jk_cell_grad";
-    TGCN_CHECK(check_sizes(fn, R, H, H));
-    TGCN_JK_LD("ldg", ldg, 4 * int64_t(H));
-    TGCN_JK_LD("lddg", lddg, 4 * int64_t(H));
-    TGCN_JK_LD("ldc", ldc, H);
-    TGCN_JK_LD("lddc", lddc, H);
-    TGCN_JK_LD("ldds", ldds, 1);
-    if (c_prev) TGCN_JK_LD("ldcp", ldcp, H);
-    if (dh_rec) TGCN_JK_LD("lddh", lddh, H);
+    TGCN_CHECK(check_widths(fn, R, H, H));
+    TGCN_CHECK(check_ld(fn, "ldg", ldg, 4 * int64_t(H)));
+    TGCN_CHECK(check_ld(fn, "lddg", lddg, 4 * int64_t(H)));
+    TGCN_CHECK(check_ld(fn, "ldc", ldc, H));
+    TGCN_CHECK(check_ld(fn, "lddc", lddc, H));
+    TGCN_CHECK(check_ld(fn, "ldds", ldds, 1));
+    if (c_prev) TGCN_CHECK(check_ld(fn, "ldcp", ldcp, H));
+    if (dh_rec) TGCN_CHECK(check_ld(fn, "lddh", lddh, H));
     if (R == 0) return TGCN_OK;
-    TGCN_JK_PTR("gates", gates);
-    TGCN_JK_PTR("c", c);
-    TGCN_JK_PTR("dscore_t", dscore_t);
-    TGCN_JK_PTR("att_w_dir", att_w_dir);
-    TGCN_JK_PTR("dc", dc);
-    TGCN_JK_PTR("dgates", dgates);
+    TGCN_CHECK(check_ptr(fn, "gates", gates));
+    TGCN_CHECK(check_ptr(fn, "c", c));
+    TGCN_CHECK(check_ptr(fn, "dscore_t", dscore_t));
+    TGCN_CHECK(check_ptr(fn, "att_w_dir", att_w_dir));
+    TGCN_CHECK(check_ptr(fn, "dc", dc));
+    TGCN_CHECK(check_ptr(fn, "dgates", dgates));
     hipLaunchKernelGGL(k_jk_cell_grad, dim3(grid_of(R * H)), dim3(256), 0, static_cast<hipStream_t>(stream), gates, ldg, c, ldc,
                        c_prev, ldcp, dh_rec, lddh, dscore_t, ldds, att_w_dir, dc, lddc, dc_zero, dgates, lddg, R, H);
     TGCN_HIP_CHECK(hipGetLastError());
@@ -526,17 +511,17 @@ int tgcn_jk_input_grad(float *dx, int64_t lddx, const float *T, int64_t ldt, con
                        int64_t ldo, const float *alpha_t, int64_t lda, int64_t R, int C, tgcn_stream stream) {
     using namespace tgcn;
     const char *fn = "tgcn_jk_input_grad";
-    TGCN_CHECK(check_sizes(fn, R, C, C));
-    TGCN_JK_LD("lddx", lddx, C);
-    TGCN_JK_LD("ldt", ldt, C);
-    TGCN_JK_LD("ldg", ldg, C);
-    if (out) TGCN_JK_LD("ldo", ldo, C);
-    TGCN_JK_LD("lda", lda, 1);
+    TGCN_CHECK(check_widths(fn, R, C, C));
+    TGCN_CHECK(check_ld(fn, "lddx", lddx, C));
+    TGCN_CHECK(check_ld(fn, "ldt", ldt, C));
+    TGCN_CHECK(check_ld(fn, "ldg", ldg, C));
+    if (out) TGCN_CHECK(check_ld(fn, "ldo", ldo, C));
+    TGCN_CHECK(check_ld(fn, "lda", lda, 1));
     if (R == 0) return TGCN_OK;
-    TGCN_JK_PTR("dx", dx);
-    TGCN_JK_PTR("T", T);
-    TGCN_JK_PTR("G", G);
-    TGCN_JK_PTR("alpha_t", alpha_t);
+    TGCN_CHECK(check_ptr(fn, "dx", dx));
+    TGCN_CHECK(check_ptr(fn, "T", T));
+    TGCN_CHECK(check_ptr(fn, "G", G));
+    TGCN_CHECK(check_ptr(fn, "alpha_t", alpha_t));
     hipLaunchKernelGGL(k_jk_input_grad, dim3(grid_of(R * C)), dim3(256), 0, static_cast<hipStream_t>(stream), dx, lddx, T, ldt,
                        G, ldg, out, ldo, alpha_t, lda, R, C);
     TGCN_HIP_CHECK(hipGetLastError());

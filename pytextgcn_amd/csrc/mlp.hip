@@ -7,54 +7,17 @@
 //                                dW[m, j] = sum_i G[i, m] a(i, j)                       (a recomputed, the same mask)
 // keep(i, j) is the decision of tgcn_gemm_*_dropout (drop_hash.h) for mask row mask_row0 + i, column j.
 //
-// All three products run on v_mfma_f32_32x32x2_f32 (exact fp32; fragment maps as in dense.hip / embed.hip: lane l feeds
-// A[l & 31][l >> 5] and B[l >> 5][l & 31], register r of lane l is C[(r & 3) + 8 (r >> 2) + 4 (l >> 5)][l & 31]).  Z, W and
-// G are row-major, so every global load here has the lanes of a half wave on 32 consecutive floats of one row (one
-// 128-byte run); they are plain dword loads, which ask nothing of the strides or the alignment.  Where the matrix cores
-// want an operand with the ROW on the lane (the forward's activation and weight tiles, dZ's tile of G), the tile goes
-// through LDS with an odd row stride.
+// All three products run on v_mfma_f32_32x32x2_f32 (fragment maps: fused_act.h).  Z, W and G are row-major, so every
+// global load here has the lanes of a half wave on 32 consecutive floats of one row (one 128-byte run); they are plain
+// dword loads, which ask nothing of the strides or the alignment.  Where the matrix cores want an operand with the ROW
+// on the lane (the forward's activation and weight tiles, dZ's tile of G), the tile goes through LDS with an odd row
+// stride.
 #include <algorithm>
 
-#include "common.h"
-#include "drop_hash.h"
+#include "fused_act.h"
 
 namespace tgcn {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// torch's constants (aten/src/ATen/native/Activation.cpp: selu), as embed.hip has them
-constexpr float kSeluScale = 1.0507009873554805f;
-constexpr float kSeluNeg = static_cast<float>(1.0507009873554805 * 1.6732632423543772);   // scale * alpha
-
-struct MlpDrop {
-    const uint64_t *seed;  // device pointer (read by the kernels: safe under HIP-graph capture)
-    uint32_t thresh;       // keep iff hash >= thresh
-    float scale;           // 1 / (1 - p)
-    int64_t row0;          // row i is mask row i + row0
-};
-
-__device__ __forceinline__ float selu_f(float x) { return x > 0.f ? kSeluScale * x : kSeluNeg * expm1f(x); }
-__device__ __forceinline__ float selu_grad_f(float x) { return x > 0.f ? kSeluScale : kSeluNeg * expf(x); }
-
-// a(i, j) from z = Z[i, j] + b[j]; `key` is row i's key, `col_term` column j's term of the hash
-template <bool DROP>
-__device__ __forceinline__ float mlp_act(float z, uint32_t key, uint32_t col_term, const MlpDrop &d) {
-    const float a = selu_f(z);
-    if constexpr (DROP) return drop_hash_keep(key, col_term, d.thresh) ? a * d.scale : 0.f;
-    return a;
-}
-
-template <bool DROP>
-__device__ __forceinline__ uint32_t mlp_row_key(const MlpDrop &d, int64_t i) {
-    if constexpr (DROP) {
-        const uint64_t seed = *d.seed;
-        return drop_row_key(static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), i + d.row0);
-    }
-    return 0u;
-}
-
-__device__ __forceinline__ int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 // ---------------------------------------------------------------------------------------------
 // Forward.  A workgroup owns 128 rows, a wave 32 of them and all 32 NT result columns.  Per chunk of 32 reduction
@@ -67,7 +30,7 @@ template <int NT, bool DROP>
 __global__ __launch_bounds__(256, 2) void k_mlp_fwd(const float *__restrict__ Z, int64_t ldz, const float *__restrict__ b,
                                                     const float *__restrict__ W, int64_t ldw, const float *__restrict__ cb,
                                                     float *__restrict__ C, int64_t ldc, int64_t N, int K, int n,
-                                                    const MlpDrop d) {
+                                                    const RowDrop d) {
     constexpr int KC = 32, NP = 32 * NT, LD = KC + 1;
     __shared__ float Ws[NP * LD];
     __shared__ float Zs[128 * LD];
@@ -77,7 +40,7 @@ __global__ __launch_bounds__(256, 2) void k_mlp_fwd(const float *__restrict__ Z,
     const int64_t row0 = blk0 + wave * 32;
     const int64_t i = row0 + c;
     const bool live = i < N;
-    const uint32_t key = mlp_row_key<DROP>(d, i);
+    const uint32_t key = row_key<DROP>(d, i);
     const int skk = tid & 31, sr = tid >> 5;               // staging: this thread's column of the chunk and its first row
     f32x16 acc[NT];
 #pragma unroll
@@ -104,7 +67,7 @@ __global__ __launch_bounds__(256, 2) void k_mlp_fwd(const float *__restrict__ Z,
 #pragma unroll
         for (int s = 0; s < KC / 2; ++s) {
             const int kk = 2 * s + half, k = k0 + kk;
-            const float a = (live && k < K) ? mlp_act<DROP>(zr[kk] + bs[kk], key, drop_col_term(k), d) : 0.f;
+            const float a = (live && k < K) ? act<DROP>(zr[kk] + bs[kk], key, drop_col_term(k), d) : 0.f;
 #pragma unroll
             for (int t = 0; t < NT; ++t)
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, Ws[(32 * t + c) * LD + kk], acc[t], 0, 0, 0);
@@ -135,7 +98,7 @@ template <int NT, bool DROP>
 __global__ __launch_bounds__(256, 2) void k_mlp_grad_z(const float *__restrict__ Z, int64_t ldz, const float *__restrict__ b,
                                                        const float *__restrict__ W, int64_t ldw,
                                                        const float *__restrict__ G, int64_t ldg, float *__restrict__ dZ,
-                                                       int64_t lddz, int64_t N, int K, int n, int accum, const MlpDrop d) {
+                                                       int64_t lddz, int64_t N, int K, int n, int accum, const RowDrop d) {
     constexpr int NP = 32 * NT;
     __shared__ float Ws[NP * 32];
     __shared__ float Gs[4 * 32 * 33];
@@ -160,7 +123,7 @@ __global__ __launch_bounds__(256, 2) void k_mlp_grad_z(const float *__restrict__
     }
     uint32_t keys[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) keys[r] = mlp_row_key<DROP>(d, row0 + acc_row(r, half));
+    for (int r = 0; r < 16; ++r) keys[r] = row_key<DROP>(d, row0 + acc_row(r, half));
 
     for (int j0 = 0; j0 < K; j0 += 32) {
         __syncthreads();                                   // the previous tile has been read
@@ -205,14 +168,12 @@ __global__ __launch_bounds__(256, 2) void k_mlp_grad_z(const float *__restrict__
 // reads 128 rows x 32 columns of Z, forms a(i, j) ONCE per element and leaves it in LDS (the row keys of the tile are
 // computed once, by 128 threads, and shared through LDS); the 4 waves split the rows m of dW (TW tiles of 32 each) and
 // read their slab of G straight from memory, 128 bytes per half wave.  The slices' partial sums go to the workspace and
-// are added in a fixed order by k_mlp_reduce_w.
+// are added in a fixed order by k_reduce_slices.
 // ---------------------------------------------------------------------------------------------
-constexpr int kWChunk = 128;   // rows per staged tile
-
 template <int TW, bool DROP>
 __global__ __launch_bounds__(256, 2) void k_mlp_grad_w(const float *__restrict__ Z, int64_t ldz, const float *__restrict__ b,
                                                        const float *__restrict__ G, int64_t ldg, float *__restrict__ part,
-                                                       int64_t N, int K, int n, int64_t chunks_per_slice, const MlpDrop d) {
+                                                       int64_t N, int K, int n, int64_t chunks_per_slice, const RowDrop d) {
     constexpr int NP = 128 * TW;
     __shared__ float As[kWChunk * 32];
     __shared__ uint32_t ks[kWChunk];
@@ -242,7 +203,7 @@ __global__ __launch_bounds__(256, 2) void k_mlp_grad_w(const float *__restrict__
         }
         __syncthreads();                                   // the previous tile has been read
         if constexpr (DROP) {
-            if (tid < kWChunk) ks[tid] = mlp_row_key<DROP>(d, i0 + tid);
+            if (tid < kWChunk) ks[tid] = row_key<DROP>(d, i0 + tid);
             __syncthreads();
         }
 #pragma unroll
@@ -250,7 +211,7 @@ __global__ __launch_bounds__(256, 2) void k_mlp_grad_w(const float *__restrict__
             const int r = sr + 8 * u;
             const int64_t i = i0 + r;
             const uint32_t key = DROP ? ks[r] : 0u;
-            As[r * 32 + sj] = (i < i_end && j < K) ? mlp_act<DROP>(z[u] + bj, key, col_term, d) : 0.f;
+            As[r * 32 + sj] = (i < i_end && j < K) ? act<DROP>(z[u] + bj, key, col_term, d) : 0.f;
         }
         __syncthreads();
         if (computes) {
@@ -275,93 +236,33 @@ __global__ __launch_bounds__(256, 2) void k_mlp_grad_w(const float *__restrict__
         for (int r = 0; r < 16; ++r) out[int64_t((wave * TW + t) * 32 + acc_row(r, half)) * kpad] = acc[t][r];
 }
 
-__global__ __launch_bounds__(256) void k_mlp_reduce_w(const float *__restrict__ part, int slices, int np, int kpad, int n,
-                                                      int K, float *__restrict__ dW, int64_t lddw) {
-    const int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x;
-    if (e >= int64_t(n) * K) return;
-    const int m = static_cast<int>(e / K), j = static_cast<int>(e % K);
-    const float *p = part + int64_t(m) * kpad + j;
-    const int64_t stride = int64_t(np) * kpad;
-    float s = 0.f;
-    for (int q = 0; q < slices; ++q) s += p[q * stride];
-    dW[int64_t(m) * lddw + j] = s;
-}
-
 constexpr int kFwdGroup = 256;   // result columns of one forward launch (8 tiles)
 constexpr int kGzGroup = 128;    // reduction length of one dZ launch (4 tiles: 64 registers of G per lane)
 constexpr int kWGroup = 256;     // rows of dW of one dW launch (4 waves x 2 tiles)
-
-// how the rows are cut into slices for dW: about 512 workgroups in all, at most 256 slices
-void grad_w_split(int64_t N, int K, int64_t &slices, int64_t &chunks_per_slice) {
-    const int64_t chunks = std::max<int64_t>(1, (N + kWChunk - 1) / kWChunk);
-    const int64_t ktiles = (int64_t(K) + 31) / 32;
-    const int64_t want = std::min<int64_t>(256, std::max<int64_t>(1, 512 / ktiles));
-    chunks_per_slice = (chunks + want - 1) / want;
-    slices = (chunks + chunks_per_slice - 1) / chunks_per_slice;
-}
+constexpr int kWTarget = 512;    // workgroups of a dW launch, about (grad_w_split)
 
 // the workspace: the column-sum partials of db first, the slices' partial sums of dW after them
 size_t db_floats(int64_t N, int K) { return static_cast<size_t>(colsum_blocks(N)) * static_cast<size_t>(K); }
 
 size_t dw_floats(int64_t N, int K, int n) {
     int64_t slices, cps;
-    grad_w_split(N, K, slices, cps);
+    grad_w_split(N, K, kWTarget, slices, cps);
     const int64_t kpad = (int64_t(K) + 31) / 32 * 32;
     const int64_t np = std::min(n, kWGroup) > 128 ? 256 : 128;
     return static_cast<size_t>(slices * np * kpad);
 }
 
-int make_mlp_drop(const char *fn, double p, const uint64_t *seed, int64_t mask_row0, MlpDrop &d, bool &on) {
-    if (!(p >= 0.0 && p < 1.0)) {
-        set_error("%s: p must be in [0, 1) (p=%g)", fn, p);
-        return TGCN_E_INVALID;
-    }
-    if (mask_row0 < 0) {
-        set_error("%s: mask_row0 must be >= 0 (%lld)", fn, (long long)mask_row0);
-        return TGCN_E_INVALID;
-    }
-    on = p > 0.0 && seed != nullptr;
-    d.seed = seed;
-    d.thresh = on ? drop_threshold(p) : 0u;
-    d.scale = on ? static_cast<float>(1.0 / (1.0 - p)) : 1.f;
-    d.row0 = mask_row0;
-    return TGCN_OK;
-}
-
-int check_sizes(const char *fn, int64_t N, int K, int n) {
-    if (N < 0 || K <= 0 || n <= 0) {
-        set_error("%s: need N >= 0, k >= 1 and n >= 1 (N=%lld, k=%d, n=%d)", fn, (long long)N, K, n);
-        return TGCN_E_INVALID;
-    }
-    return TGCN_OK;
-}
-
-#define TGCN_MLP_LD(name, ld, extent)                                                                       \
-    if ((ld) < (extent)) {                                                                                  \
-        set_error("%s: " name " (%lld) is smaller than the extent %lld", fn, (long long)(ld), (long long)(extent)); \
-        return TGCN_E_INVALID;                                                                              \
-    }
-#define TGCN_MLP_PTR(name, ptr)                              \
-    if (!(ptr)) {                                            \
-        set_error("%s: " name " is NULL", fn);               \
-        return TGCN_E_INVALID;                               \
-    }
-
 template <bool DROP>
 int launch_fwd(const float *Z, int64_t ldz, const float *b, const float *W, int64_t ldw, const float *cb, float *C,
-               int64_t ldc, int64_t N, int K, int n, const MlpDrop &d, hipStream_t s) {
+               int64_t ldc, int64_t N, int K, int n, const RowDrop &d, hipStream_t s) {
     const unsigned grid = static_cast<unsigned>((N + 127) / 128);
     for (int col0 = 0; col0 < n; col0 += kFwdGroup) {
         const int ng = std::min(n - col0, kFwdGroup), nt = (ng + 31) / 32;
         const float *cg = cb ? cb + col0 : nullptr;
-#define TGCN_MLP_FWD(NT)                                                                                                \
-    hipLaunchKernelGGL((k_mlp_fwd<NT, DROP>), dim3(grid), dim3(256), 0, s, Z, ldz, b, W + int64_t(col0) * ldw, ldw, cg, \
-                       C + col0, ldc, N, K, ng, d)
-        if (nt <= 1) TGCN_MLP_FWD(1);
-        else if (nt <= 2) TGCN_MLP_FWD(2);
-        else if (nt <= 4) TGCN_MLP_FWD(4);
-        else TGCN_MLP_FWD(8);
-#undef TGCN_MLP_FWD
+        with_tiles<1, 2, 4, 8>(nt, [&](auto NT) {
+            hipLaunchKernelGGL((k_mlp_fwd<decltype(NT)::value, DROP>), dim3(grid), dim3(256), 0, s, Z, ldz, b,
+                               W + int64_t(col0) * ldw, ldw, cg, C + col0, ldc, N, K, ng, d);
+        });
     }
     TGCN_HIP_CHECK(hipGetLastError());
     return TGCN_OK;
@@ -369,18 +270,15 @@ int launch_fwd(const float *Z, int64_t ldz, const float *b, const float *W, int6
 
 template <bool DROP>
 int launch_grad_z(const float *Z, int64_t ldz, const float *b, const float *W, int64_t ldw, const float *G, int64_t ldg,
-                  float *dZ, int64_t lddz, float *db, int64_t N, int K, int n, const MlpDrop &d, float *part,
+                  float *dZ, int64_t lddz, float *db, int64_t N, int K, int n, const RowDrop &d, float *part,
                   hipStream_t s) {
     const unsigned grid = static_cast<unsigned>((N + 127) / 128);
     for (int col0 = 0; col0 < n; col0 += kGzGroup) {
         const int ng = std::min(n - col0, kGzGroup), nt = (ng + 31) / 32, accum = col0 > 0;
-#define TGCN_MLP_GZ(NT)                                                                                                   \
-    hipLaunchKernelGGL((k_mlp_grad_z<NT, DROP>), dim3(grid), dim3(256), 0, s, Z, ldz, b, W + int64_t(col0) * ldw, ldw,    \
-                       G + col0, ldg, dZ, lddz, N, K, ng, accum, d)
-        if (nt <= 1) TGCN_MLP_GZ(1);
-        else if (nt <= 2) TGCN_MLP_GZ(2);
-        else TGCN_MLP_GZ(4);
-#undef TGCN_MLP_GZ
+        with_tiles<1, 2, 4>(nt, [&](auto NT) {
+            hipLaunchKernelGGL((k_mlp_grad_z<decltype(NT)::value, DROP>), dim3(grid), dim3(256), 0, s, Z, ldz, b,
+                               W + int64_t(col0) * ldw, ldw, G + col0, ldg, dZ, lddz, N, K, ng, accum, d);
+        });
     }
     TGCN_HIP_CHECK(hipGetLastError());
     // db[j] = sum_i dZ[i, j]: tgcn_colsum's two passes (colsum.hip), a fixed summation order
@@ -389,9 +287,9 @@ int launch_grad_z(const float *Z, int64_t ldz, const float *b, const float *W, i
 
 template <bool DROP>
 int launch_grad_w(const float *Z, int64_t ldz, const float *b, const float *G, int64_t ldg, float *dW, int64_t lddw,
-                  int64_t N, int K, int n, const MlpDrop &d, float *part, hipStream_t s) {
+                  int64_t N, int K, int n, const RowDrop &d, float *part, hipStream_t s) {
     int64_t slices, cps;
-    grad_w_split(N, K, slices, cps);
+    grad_w_split(N, K, kWTarget, slices, cps);
     const int ktiles = (K + 31) / 32, kpad = ktiles * 32;
     for (int m0 = 0; m0 < n; m0 += kWGroup) {
         const int ng = std::min(n - m0, kWGroup);
@@ -401,9 +299,7 @@ int launch_grad_w(const float *Z, int64_t ldz, const float *b, const float *G, i
         else
             hipLaunchKernelGGL((k_mlp_grad_w<1, DROP>), grid, dim3(256), 0, s, Z, ldz, b, G + m0, ldg, part, N, K, ng, cps, d);
         const int np = ng > 128 ? 256 : 128;
-        const unsigned rgrid = static_cast<unsigned>((int64_t(ng) * K + 255) / 256);
-        hipLaunchKernelGGL(k_mlp_reduce_w, dim3(rgrid), dim3(256), 0, s, part, static_cast<int>(slices), np, kpad, ng, K,
-                           dW + int64_t(m0) * lddw, lddw);
+        launch_reduce_slices(part, slices, int64_t(np) * kpad, kpad, ng, K, dW + int64_t(m0) * lddw, lddw, s);
     }
     TGCN_HIP_CHECK(hipGetLastError());
     return TGCN_OK;
@@ -419,18 +315,18 @@ int tgcn_mlp_act_linear(const float *Z, int64_t ldz, const float *b, const float
                         tgcn_stream stream) {
     using namespace tgcn;
     const char *fn = "tgcn_mlp_act_linear";
-    TGCN_CHECK(check_sizes(fn, N, k, n));
-    MlpDrop d{};
+    TGCN_CHECK(check_sizes(fn, "k", N, k, n));
+    RowDrop d{};
     bool drop = false;
-    TGCN_CHECK(make_mlp_drop(fn, p, seed, mask_row0, d, drop));
-    TGCN_MLP_LD("ldz", ldz, k);
-    TGCN_MLP_LD("ldw", ldw, k);
-    TGCN_MLP_LD("ldc", ldc, n);
+    TGCN_CHECK(make_row_drop(fn, p, seed, mask_row0, d, drop));
+    TGCN_CHECK(check_ld(fn, "ldz", ldz, k));
+    TGCN_CHECK(check_ld(fn, "ldw", ldw, k));
+    TGCN_CHECK(check_ld(fn, "ldc", ldc, n));
     if (N == 0) return TGCN_OK;                // (an empty tensor's pointer may be NULL)
-    TGCN_MLP_PTR("Z", Z);
-    TGCN_MLP_PTR("b", b);
-    TGCN_MLP_PTR("W", W);
-    TGCN_MLP_PTR("C", C);
+    TGCN_CHECK(check_ptr(fn, "Z", Z));
+    TGCN_CHECK(check_ptr(fn, "b", b));
+    TGCN_CHECK(check_ptr(fn, "W", W));
+    TGCN_CHECK(check_ptr(fn, "C", C));
     hipStream_t s = static_cast<hipStream_t>(stream);
     return drop ? launch_fwd<true>(Z, ldz, b, W, ldw, c, C, ldc, N, k, n, d, s)
                 : launch_fwd<false>(Z, ldz, b, W, ldw, c, C, ldc, N, k, n, d, s);
@@ -447,19 +343,15 @@ int tgcn_mlp_act_linear_grad(const float *Z, int64_t ldz, const float *b, const 
                              size_t workspace_bytes, tgcn_stream stream) {
     using namespace tgcn;
     const char *fn = "tgcn_mlp_act_linear_grad";
-    TGCN_CHECK(check_sizes(fn, N, k, n));
-    MlpDrop d{};
+    TGCN_CHECK(check_sizes(fn, "k", N, k, n));
+    RowDrop d{};
     bool drop = false;
-    TGCN_CHECK(make_mlp_drop(fn, p, seed, mask_row0, d, drop));
-    TGCN_MLP_LD("ldz", ldz, k);
-    TGCN_MLP_LD("ldw", ldw, k);
-    TGCN_MLP_LD("ldg", ldg, n);
-    if (dZ) {
-        TGCN_MLP_LD("lddz", lddz, k);
-    }
-    if (dW) {
-        TGCN_MLP_LD("lddw", lddw, k);
-    }
+    TGCN_CHECK(make_row_drop(fn, p, seed, mask_row0, d, drop));
+    TGCN_CHECK(check_ld(fn, "ldz", ldz, k));
+    TGCN_CHECK(check_ld(fn, "ldw", ldw, k));
+    TGCN_CHECK(check_ld(fn, "ldg", ldg, n));
+    if (dZ) TGCN_CHECK(check_ld(fn, "lddz", lddz, k));
+    if (dW) TGCN_CHECK(check_ld(fn, "lddw", lddw, k));
     if ((dZ == nullptr) != (db == nullptr) && N > 0) {     // (N == 0: dZ has no element and its pointer may be NULL)
         set_error("%s: dZ and db are computed together: pass both or neither (db is the column sum of dZ)", fn);
         return TGCN_E_INVALID;
@@ -470,10 +362,10 @@ int tgcn_mlp_act_linear_grad(const float *Z, int64_t ldz, const float *b, const 
         if (dW) TGCN_HIP_CHECK(hipMemset2DAsync(dW, sizeof(float) * lddw, 0, sizeof(float) * k, n, s));
         return TGCN_OK;
     }
-    TGCN_MLP_PTR("Z", Z);
-    TGCN_MLP_PTR("b", b);
-    TGCN_MLP_PTR("W", W);
-    TGCN_MLP_PTR("G", G);
+    TGCN_CHECK(check_ptr(fn, "Z", Z));
+    TGCN_CHECK(check_ptr(fn, "b", b));
+    TGCN_CHECK(check_ptr(fn, "W", W));
+    TGCN_CHECK(check_ptr(fn, "G", G));
     if (!dZ && !dW) {
         set_error("%s: dZ (with db) and dW are both NULL: nothing to compute", fn);
         return TGCN_E_INVALID;
