@@ -541,6 +541,47 @@ int tgcn_mlp_act_linear_grad(const float *Z, int64_t ldz, const float *b, const 
                              size_t workspace_bytes, tgcn_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The same products with a weight that depends on the row's GROUP: the K per-label MLPs of the reference's MLP_label.py
+ * as one network.  The N rows lie in grouped order: rows [row_ptr[g], row_ptr[g + 1]) belong to group g (0 <= g < K <= 128;
+ * an empty group is legal), rows at or past row_ptr[K] to nobody: they are neither read nor written.  Group g reads rows
+ * [w_row0[g], w_row0[g] + n[g]) of the stacked weight W [w_rows, k], entries [b_off[g], b_off[g] + k) of the stacked bias
+ * b [b_len], and owns columns [col0[g], col0[g] + n[g]) of C and G [N, c_cols] (and of c [c_cols]).  For row i of group g,
+ * with a(i, j) = s * keep(i, j) * selu(Z[i, j] + b[b_off[g] + j]) and keep the hash above for mask row mask_row0 + i:
+ *   tgcn_mlp_grouped_act_linear        C[i, col0[g] + m] = sum_j a(i, j) W[w_row0[g] + m, j] (+ c[col0[g] + m])    m < n[g]
+ *   tgcn_mlp_grouped_act_linear_grad   dZ[i, j] = s keep selu'(.) sum_m G[i, col0[g] + m] W[w_row0[g] + m, j]
+ *                                      db[b_off[g] + j]      = the sum of dZ[i, j] over the rows of group g
+ *                                      dW[w_row0[g] + m, j]  = the sum of G[i, col0[g] + m] a(i, j) over the rows of group g
+ *                                      dc[col0[g] + m]       = the sum of G[i, col0[g] + m] over the rows of group g
+ *                                                              (the gradient of c; dc [c_cols] or NULL; asks for column
+ *                                                              ranges that do not overlap, as the class segments are)
+ * Every other element of C, dZ, db, dW and dc keeps what it held; db, dW and dc of a group without rows are exact zeros.  Group
+ * g's slices of C and dZ carry the bits of tgcn_mlp_act_linear / _grad on rows [row_ptr[g], row_ptr[g + 1]) with mask_row0
+ * + row_ptr[g]: the same kernels (v_mfma_f32_32x32x2_f32), a workgroup serving one tile of at most 128 rows of one group.
+ *
+ * tgcn_mlp_grouped_layout (HOST only: no device is touched, nothing is enqueued) validates the description and fills
+ * `out` (tgcn_mlp_grouped_layout_bytes(K, row_ptr) bytes, an upper bound that does not depend on k; 0 for an invalid K or
+ * row_ptr) with the tables the kernels read: the groups, the row tiles and the slices of the dW reduction.  The caller
+ * copies the blob to the device once and passes BOTH copies to the products (`layout_host` is read during the call for the
+ * grid sizes and the checks, `layout_dev` by the kernels), so the products enqueue on `stream` only: no allocation, no
+ * copy, no synchronisation, legal under HIP-graph capture.  The launch count depends on max n[g] and k (column groups of
+ * 256, 128 and 256 as above), never on K.  Fixed summation orders, no atomics.  K outside [1, 128], a decreasing row_ptr,
+ * row_ptr[K] > N, n[g] < 1, a range of W, C or b outside w_rows, c_cols or b_len, a short `out`, and in the products a
+ * layout built for another N or k, a leading dimension below the width (ldc, ldg >= c_cols), NULL operands and a short
+ * workspace are TGCN_E_INVALID before anything is enqueued.  dZ and db together or neither, dW on its own, as above. */
+size_t tgcn_mlp_grouped_layout_bytes(int K, const int64_t *row_ptr);
+int tgcn_mlp_grouped_layout(int K, const int64_t *row_ptr, const int32_t *w_row0, const int32_t *n, const int32_t *col0,
+                            const int32_t *b_off, int64_t N, int k, int64_t w_rows, int64_t c_cols, int64_t b_len, void *out,
+                            size_t out_bytes);
+int tgcn_mlp_grouped_act_linear(const float *Z, int64_t ldz, const float *b, const float *W, int64_t ldw, const float *c,
+                                float *C, int64_t ldc, int64_t N, int k, const void *layout_host, const void *layout_dev,
+                                double p, const uint64_t *seed, int64_t mask_row0, tgcn_stream stream);
+size_t tgcn_mlp_grouped_act_linear_grad_workspace_bytes(const void *layout_host);
+int tgcn_mlp_grouped_act_linear_grad(const float *Z, int64_t ldz, const float *b, const float *W, int64_t ldw, const float *G,
+                                     int64_t ldg, float *dZ, int64_t lddz, float *db, float *dW, int64_t lddw, float *dc,
+                                     int64_t N, int k, const void *layout_host, const void *layout_dev, double p, const uint64_t *seed,
+                                     int64_t mask_row0, void *workspace, size_t workspace_bytes, tgcn_stream stream);
+
+/* ---------------------------------------------------------------------------------------------
  * JumpingKnowledge(mode="lstm") of the reference's JumpingKnowledgeNetwork (textgcn/lib/models.py:64,75; PyG 1.6.3): a
  * bidirectional LSTM of hidden width H over the L per-layer activations x_t [N, C] of every node, a Linear(2 H -> 1) on
  * [h_fwd_t | h_bwd_t], a softmax over the layers and the weighted sum

@@ -119,6 +119,12 @@ inline void grad_w_split(int64_t N, int K, int target_workgroups, int64_t &slice
     slices = (chunks + chunks_per_slice - 1) / chunks_per_slice;
 }
 
+// How the fused SELU + dropout products of the MLP (mlp.hip, mlp_grouped.hip) cut a wide operand into launches.
+constexpr int kFwdGroup = 256;   // result columns of one forward launch (8 tiles)
+constexpr int kGzGroup = 128;    // reduction length of one dZ launch (4 tiles: 64 registers of G per lane)
+constexpr int kWGroup = 256;     // rows of dW of one dW launch (4 waves x 2 tiles)
+constexpr int kWTarget = 512;    // workgroups of a dW launch, about (grad_w_split)
+
 namespace {   // (a kernel in a header: every translation unit that launches it has its own; as a template, no other has one)
 
 // out[r, j] = sum over the slices q, in order, of part[q * slice_stride + r * row_stride + j]

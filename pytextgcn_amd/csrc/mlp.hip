@@ -236,11 +236,6 @@ __global__ __launch_bounds__(256, 2) void k_mlp_grad_w(const float *__restrict__
         for (int r = 0; r < 16; ++r) out[int64_t((wave * TW + t) * 32 + acc_row(r, half)) * kpad] = acc[t][r];
 }
 
-constexpr int kFwdGroup = 256;   // result columns of one forward launch (8 tiles)
-constexpr int kGzGroup = 128;    // reduction length of one dZ launch (4 tiles: 64 registers of G per lane)
-constexpr int kWGroup = 256;     // rows of dW of one dW launch (4 waves x 2 tiles)
-constexpr int kWTarget = 512;    // workgroups of a dW launch, about (grad_w_split)
-
 // the workspace: the column-sum partials of db first, the slices' partial sums of dW after them
 size_t db_floats(int64_t N, int K) { return static_cast<size_t>(colsum_blocks(N)) * static_cast<size_t>(K); }
 

@@ -3,6 +3,6 @@ perlevel_amazon.py:14 `from textgcn.lib.models import JumpingKnowledgeNetwork, G
 MLP_flat.py `from textgcn.lib.models import MLP`).  `PerLabelGCN` has no counterpart there: it is the K `GCN`s of
 perlabel_amazon.py:113 as one network (pytextgcn_amd/perlabel.py)."""
 from ..models import EGCN, GCN, MLP, JumpingKnowledgeNetwork
-from ..perlabel import PerLabelGCN
+from ..perlabel import PerLabelGCN, PerLabelMLP
 
-__all__ = ["GCN", "EGCN", "JumpingKnowledgeNetwork", "MLP", "PerLabelGCN"]
+__all__ = ["GCN", "EGCN", "JumpingKnowledgeNetwork", "MLP", "PerLabelGCN", "PerLabelMLP"]

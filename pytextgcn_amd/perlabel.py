@@ -24,8 +24,8 @@ import numpy as np
 import torch
 from torch import Tensor, nn
 
-from . import dense, functional, models
-from .conv import GCNConv, propagate
+from . import dense, functional, mlp, models
+from .conv import GCNConv, features_times, propagate
 from .plan import _require_cuda, note_colsum
 
 
@@ -303,5 +303,284 @@ class PerLabelGCN(nn.Module):
             m.layers[0].bias.copy_(first.bias[k * h:(k + 1) * h])
             m.layers[1].weight.copy_(second.weight[:, s:s + c])
             m.layers[1].bias.copy_(second.bias[s:s + c])
+            out.append(m.train(self.training))
+        return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The per-label strategy of the bag-of-words baseline (MLP_label.py): one `MLP(in, C_k, [256, 128])` per top-level label,
+# trained on that label's documents.  A document belongs to exactly ONE member, so the K members are one MLP whose weight
+# depends on the row's group: the rows are put in grouped order once per split (`GroupedRows`), layer 1 is the existing
+# SpMM on features whose column ids are shifted by group * F, and every later layer is `mlp.grouped_act_linear`.
+# ---------------------------------------------------------------------------------------------------------------------
+class GroupedRows:
+    """The rows of one split (train, val or routed test) in grouped order, built once on the host.
+
+    `group` [N]: the member of every row, -1 = none (an unrouted document).  `order` (int64 [N]) is the stable sort by
+    group with the -1 rows last, `row_ptr` (K + 1 ints) the segment boundaries, `n_routed = row_ptr[K]`; `group_sorted`
+    (int32 [N]) is `group[order]`, the tensor `grouped_masked_cross_entropy` takes, `routed` (bool [N]) its rows with a group.  `to(device)` moves the index tensors;
+    the per-layer layout blobs of `mlp.GroupedLayout` are cached here per device."""
+
+    def __init__(self, group, n_groups: int):
+        g = np.asarray(torch.as_tensor(group).cpu()).astype(np.int64).ravel()
+        K = int(n_groups)
+        if K < 1:
+            raise ValueError("GroupedRows: n_groups must be >= 1")
+        if g.size and (g.min() < -1 or g.max() >= K):
+            raise ValueError(f"GroupedRows: groups must lie in [-1, {K}) (found {int(g.min())} .. {int(g.max())})")
+        key = np.where(g < 0, K, g)
+        order = np.argsort(key, kind="stable")
+        counts = np.bincount(key, minlength=K + 1)[:K]
+        self.n_groups, self.n_rows = K, int(g.size)
+        self.row_ptr = [0] + np.cumsum(counts).tolist()
+        self.n_routed = int(self.row_ptr[K])
+        self.order = torch.from_numpy(order)
+        self.group_sorted = torch.from_numpy(g[order].astype(np.int32))
+        self.routed = self.group_sorted >= 0               # (one object: the loss counts a mask's rows once per object)
+        self._group = torch.from_numpy(g)
+        pos = np.empty_like(order)
+        pos[order] = np.arange(order.size)
+        self._pos = torch.from_numpy(pos)                  # row of the caller's order -> row in grouped order
+        self._layouts: dict = {}
+
+    def to(self, device) -> "GroupedRows":
+        for name in ("order", "group_sorted", "routed", "_group", "_pos"):
+            setattr(self, name, getattr(self, name).to(device))
+        return self
+
+    def _on(self, t: Tensor, name: str) -> Tensor:
+        idx = getattr(self, name)
+        if idx.device != t.device:
+            raise RuntimeError(f"GroupedRows lives on {idx.device}, the tensor on {t.device}: call rows.to(device) once")
+        return idx
+
+    def take(self, t: Tensor) -> Tensor:
+        """A per-row tensor [N, ...] in grouped order."""
+        if t.size(0) != self.n_rows:
+            raise ValueError(f"GroupedRows.take: {t.size(0)} rows, the split has {self.n_rows}")
+        return t.index_select(0, self._on(t, "order"))
+
+    def restore(self, t: Tensor, fill=-1) -> Tensor:
+        """A per-row tensor in grouped order back in the caller's order; rows without a group hold `fill`."""
+        if t.size(0) != self.n_rows:
+            raise ValueError(f"GroupedRows.restore: {t.size(0)} rows, the split has {self.n_rows}")
+        out = torch.full_like(t, fill)
+        routed = self._on(t, "order")[:self.n_routed]
+        out.index_copy_(0, routed, t[:self.n_routed])
+        return out
+
+    def features(self, x: Tensor) -> Tensor:
+        """Sparse COO / CSR features [N, F] -> coalesced sparse COO [N, K F] in grouped order: the entry (i, j) of a row of
+        group g sits at (position of i, g F + j), so `x' @ stack_k(W1_k)` is every row times its own member's W1.  Rows
+        without a group are empty."""
+        if x.layout not in (torch.sparse_coo, torch.sparse_csr) or x.dim() != 2:
+            raise TypeError("GroupedRows.features takes a sparse COO or CSR [N, F] matrix")
+        if x.size(0) != self.n_rows:
+            raise ValueError(f"GroupedRows.features: {x.size(0)} rows, the split has {self.n_rows}")
+        xc = (x.to_sparse_coo() if x.layout == torch.sparse_csr else x).coalesce()
+        idx, val = xc.indices(), xc.values()
+        g = self._on(val, "_group")[idx[0]]
+        keep = g >= 0
+        rows = self._on(val, "_pos")[idx[0]][keep]
+        cols = (idx[1] + g * x.size(1))[keep]
+        return torch.sparse_coo_tensor(torch.stack([rows, cols]), val[keep],
+                                       (self.n_rows, self.n_groups * x.size(1))).coalesce()
+
+    def layout(self, w_row0, n, col0, b_off, k: int, w_rows: int, c_cols: int, b_len: int, device) -> mlp.GroupedLayout:
+        """The cached `mlp.GroupedLayout` of one layer on `device`."""
+        key = (tuple(w_row0), tuple(n), tuple(col0), tuple(b_off), k, w_rows, c_cols, b_len, torch.device(device))
+        hit = self._layouts.get(key)
+        if hit is None:
+            hit = self._layouts[key] = mlp.GroupedLayout(self.row_ptr, w_row0, n, col0, b_off, self.n_rows, k, w_rows,
+                                                         c_cols, b_len, device)
+        return hit
+
+
+class PerLabelMLP(nn.Module):
+    """The K `MLP(in_channels, C_k, hidden, dropout)` of MLP_label.py as one network (equal `in_channels` and `hidden`).
+
+    `layers[0]` is an `EmbeddingLinear(K F, h_1)` whose bias is [K h_1]: member k owns the input columns [k F, (k + 1) F)
+    and the bias slice [k h_1, (k + 1) h_1).  `layers[i]`, 0 < i < L, is an `EmbeddingLinear(h_i, K h_{i+1})`: member k owns
+    the weight rows and bias entries [k h_{i+1}, (k + 1) h_{i+1}).  The last layer is an `EmbeddingLinear(h_L, n_cols)`:
+    member k owns rows [seg_start[k], seg_start[k] + C_k) (`segment_layout`; the pad rows are zero, stay zero and are never
+    read).  Every member's slice is initialised with torch's `nn.Linear` default bounds for the MEMBER's fan-in.
+
+    `forward(xg, rows)` takes `xg = rows.features(x)` and returns Zcat [N, n_cols] in grouped order: the logits of a row in
+    its member's segment, zero elsewhere -- what `functional.grouped_masked_cross_entropy` takes with `rows.group_sorted`.
+
+    The fused path (`mlp.grouped_act_linear`, one product per layer whatever K is) follows `MLP.takes_fused_path`: eval
+    mode, rate 0, or training with 0 < rate < 1 while `enable_fused_dropout()` is on.  Everything else, and everything
+    after `enable_fused_mlp(False)`, is composed group by group from `torch.selu`, `self.dropout` and `dense.xw`.
+
+    Not built: per-member early stopping (the members train in lock step), `hidden` differing between members, more than
+    128 groups, the `append_feats` form of MLP_level.py, several GPUs."""
+
+    def __init__(self, in_channels, class_counts, hidden, dropout=0.5):
+        super().__init__()
+        self.class_counts = tuple(int(c) for c in class_counts)
+        self.hidden = tuple(int(h) for h in hidden)
+        if not self.class_counts or not self.hidden:
+            raise ValueError("PerLabelMLP needs at least one group and one hidden layer")
+        if len(self.class_counts) > 128:
+            raise ValueError("PerLabelMLP: at most 128 groups")
+        self.in_channels = int(in_channels)
+        self.dropout = nn.Dropout(p=dropout)
+        self.act = nn.SELU()
+        K, F = len(self.class_counts), self.in_channels
+        starts, n_cols = segment_layout(self.class_counts)
+        self.seg_start, self.n_cols = tuple(starts), n_cols
+        first = models.EmbeddingLinear(K * F, self.hidden[0])
+        first.bias = nn.Parameter(torch.zeros(K * self.hidden[0]))
+        ls = [first]
+        ls += [models.EmbeddingLinear(h1, K * h2) for h1, h2 in zip(self.hidden, self.hidden[1:])]
+        ls += [models.EmbeddingLinear(self.hidden[-1], n_cols)]
+        self.layers = nn.ModuleList(ls)
+        self.reset_parameters()
+
+    def reset_parameters(self) -> None:
+        """torch's `nn.Linear.reset_parameters` per member: weight and bias uniform in +-1 / sqrt(fan_in of the member)."""
+        sizes = (self.in_channels,) + self.hidden
+        with torch.no_grad():
+            for layer, fan_in in zip(self.layers, sizes):
+                a = 1.0 / math.sqrt(fan_in)
+                layer.weight.uniform_(-a, a)
+                layer.bias.uniform_(-a, a)
+            last = self.layers[-1]
+            own = torch.zeros(self.n_cols, dtype=torch.bool)
+            for s, c in zip(self.seg_start, self.class_counts):
+                own[s:s + c] = True
+            last.weight[~own] = 0.0
+            last.bias[~own] = 0.0
+
+    @property
+    def n_groups(self) -> int:
+        return len(self.class_counts)
+
+    @property
+    def seg_width(self):
+        return self.class_counts
+
+    def takes_fused_path(self, x=None) -> bool:
+        p = float(self.dropout.p)
+        if not models._FUSED_MLP:
+            return False
+        return not (self.training and p != 0.0 and not (models._FUSED_DROPOUT and 0.0 < p < 1.0))
+
+    def _member(self, i: int, g: int):
+        """(first row, rows, first output column) of member g in layer i >= 1."""
+        if i == len(self.layers) - 1:
+            return self.seg_start[g], self.class_counts[g], self.seg_start[g]
+        n = self.hidden[i]
+        return g * n, n, 0
+
+    def _check(self, xg, rows) -> None:
+        _require_cuda(xg, "xg")
+        if not isinstance(rows, GroupedRows) or rows.n_groups != self.n_groups:
+            raise ValueError(f"PerLabelMLP: `rows` must be a GroupedRows of {self.n_groups} groups"
+                             + (f" (it has {rows.n_groups})" if isinstance(rows, GroupedRows) else ""))
+        if xg.dim() != 2 or xg.size(1) != self.n_groups * self.in_channels or xg.size(0) != rows.n_rows:
+            raise ValueError(f"PerLabelMLP: features {tuple(xg.shape)} do not fit {rows.n_rows} rows of {self.n_groups} x "
+                             f"{self.in_channels} columns (pass rows.features(x))")
+        if xg.dtype != torch.float32:
+            raise TypeError(f"PerLabelMLP takes float32 features, got {xg.dtype}")
+
+    def forward(self, xg, rows: GroupedRows) -> Tensor:
+        self._check(xg, rows)
+        K, first, L = self.n_groups, self.layers[0], len(self.layers) - 1
+        z = features_times(xg, first.weight.t(), first.in_features)        # no bias: the next product adds it
+        if self.takes_fused_path():
+            p = float(self.dropout.p) if self.training else 0.0
+            for i in range(1, L + 1):
+                prev, layer = self.layers[i - 1], self.layers[i]
+                k = self.hidden[i - 1]
+                w_row0, n, col0 = zip(*[self._member(i, g) for g in range(K)])
+                lay = rows.layout(w_row0, n, col0, [g * k for g in range(K)], k, layer.weight.size(0),
+                                  self.hidden[i] if i < L else self.n_cols, K * k, z.device)
+                z = mlp.grouped_act_linear(z, prev.bias, layer.weight, layer.bias if i == L else None, lay, p)
+            return z
+        out = torch.zeros(rows.n_rows, self.n_cols, dtype=torch.float32, device=z.device)
+        for g in range(K):
+            r0, r1 = rows.row_ptr[g], rows.row_ptr[g + 1]
+            if r0 == r1:
+                continue
+            a = z[r0:r1]
+            for i in range(1, L + 1):
+                k = self.hidden[i - 1]
+                w0, n, _ = self._member(i, g)
+                a = self.dropout(torch.selu(a + self.layers[i - 1].bias[g * k:(g + 1) * k]))
+                a = dense.xw(a, self.layers[i].weight[w0:w0 + n].t())
+            s, c = self.seg_start[g], self.class_counts[g]
+            out[r0:r1, s:s + c] = a + self.layers[L].bias[s:s + c]
+        return out
+
+    def loss(self, xg, rows: GroupedRows, target, mask=None, return_pred=False, class_map=None):
+        """`grouped_masked_cross_entropy` of `self(xg, rows)` -- the sum over the members of CrossEntropyLoss('mean') on
+        their own rows: `(loss, loss_k[, pred])`.  `target` (int64 [N], grouped order: `rows.take`) holds the LOCAL class
+        (`relabel`), `mask` (bool [N], grouped order; default: every routed row) the rows that count."""
+        z = self(xg, rows)
+        group = rows._on(z, "group_sorted")
+        if mask is None:
+            mask = rows.routed
+        return functional.grouped_masked_cross_entropy(z, target, mask, group, self.seg_start, self.seg_width, None,
+                                                       return_pred, None, class_map)
+
+    @torch.no_grad()
+    def predict(self, xg, rows: GroupedRows, class_map=None) -> Tensor:
+        """MLP_label.py:157-162 for every routed row at once: int64 [N] in GROUPED order (apply `rows.restore`), the arg-max
+        of the row's member as a column of Zcat or, through `class_map` (`column_class_map`), as the global class; -1 on
+        rows without a group."""
+        z = self(xg, rows)
+        n = z.size(0)
+        group = rows._on(z, "group_sorted")
+        nothing = torch.zeros(n, dtype=torch.bool, device=z.device)
+        return functional.grouped_masked_cross_entropy(
+            z, torch.zeros(n, dtype=torch.int64, device=z.device), nothing, group, self.seg_start, self.seg_width,
+            counts=[0] * self.n_groups, return_pred=True, route=group, class_map=class_map)[2]
+
+    @classmethod
+    def from_members(cls, members: Sequence[nn.Module], dropout: Optional[float] = None) -> "PerLabelMLP":
+        """One network from K `MLP`s (or modules with the same `layers.{i}.{weight,bias}`, such as the reference's
+        checkpoints loaded into `MLP`) of equal input and hidden widths.  Parameters are copied."""
+        members = list(members)
+        if not members:
+            raise ValueError("from_members: no member")
+        shapes = [[tuple(layer.weight.shape) for layer in m.layers] for m in members]
+        if any(len(s) != len(shapes[0]) or len(s) < 2 or s[:-1] != shapes[0][:-1] or s[-1][1] != shapes[0][-1][1]
+               for s in shapes):
+            raise ValueError("from_members: members must be MLPs of equal input width and equal hidden widths")
+        if any(layer.bias is None for m in members for layer in m.layers):
+            raise ValueError("from_members: members must carry biases")
+        hidden = [s[0] for s in shapes[0][:-1]]
+        rate = dropout if dropout is not None else (members[0].dropout.p if isinstance(members[0].dropout, nn.Dropout)
+                                                    else members[0].dropout)
+        net = cls(shapes[0][0][1], [s[-1][0] for s in shapes], hidden, dropout=rate).to(members[0].layers[0].weight.device)
+        F, L = net.in_channels, len(net.layers) - 1
+        with torch.no_grad():
+            net.layers[L].weight.zero_()
+            net.layers[L].bias.zero_()
+            for g, m in enumerate(members):
+                h1 = hidden[0]
+                net.layers[0].weight[:, g * F:(g + 1) * F].copy_(m.layers[0].weight)
+                net.layers[0].bias[g * h1:(g + 1) * h1].copy_(m.layers[0].bias)
+                for i in range(1, L + 1):
+                    w0, n, _ = net._member(i, g)
+                    net.layers[i].weight[w0:w0 + n].copy_(m.layers[i].weight)
+                    net.layers[i].bias[w0:w0 + n].copy_(m.layers[i].bias)
+        return net
+
+    @torch.no_grad()
+    def export_members(self) -> List[nn.Module]:
+        """K `MLP(in_channels, C_k, hidden, dropout)` holding COPIES of the members' parameters, in this network's training
+        mode: what MLP_label.py trains one by one."""
+        F, L, out = self.in_channels, len(self.layers) - 1, []
+        for g, c in enumerate(self.class_counts):
+            m = models.MLP(F, c, list(self.hidden), dropout=self.dropout.p).to(self.layers[0].weight.device)
+            h1 = self.hidden[0]
+            m.layers[0].weight.copy_(self.layers[0].weight[:, g * F:(g + 1) * F])
+            m.layers[0].bias.copy_(self.layers[0].bias[g * h1:(g + 1) * h1])
+            for i in range(1, L + 1):
+                w0, n, _ = self._member(i, g)
+                m.layers[i].weight.copy_(self.layers[i].weight[w0:w0 + n])
+                m.layers[i].bias.copy_(self.layers[i].bias[w0:w0 + n])
             out.append(m.train(self.training))
         return out
