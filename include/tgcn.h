@@ -540,6 +540,33 @@ int tgcn_mlp_act_linear_grad(const float *Z, int64_t ldz, const float *b, const 
                              int n, double p, const uint64_t *seed, int64_t mask_row0, void *workspace,
                              size_t workspace_bytes, tgcn_stream stream);
 
+/* The same products with a bias that depends on the ROW: the first hidden layer of the per-level MLP (MLP_level.py trains
+ * every level after the first on append_feats(X, H), H the one-hot columns of the levels above).  Additive to ABI 7.
+ * [X | H] @ W1.t() = X @ W1[:, :F].t() + Wh[class], so the class features are S <= 2 rows of a small table: cls int32
+ * [N, S] (row-major, leading dimension ldcls >= S, S in {1, 2}) holds row indices into T [Fh, k] (leading dimension
+ * ldt >= k, 1 <= Fh <= tgcn_hier_max_features() = 128), and the pre-activation of element (i, j) is
+ *       z(i, j) = ((Z[i, j] + T[cls[i, 0], j]) + T[cls[i, 1], j]) + b[j]          (S == 1: no second term)
+ * in exactly this order, in all three products: a(i, j) = s keep(i, j) selu(z(i, j)) in C and dW, selu'(z(i, j)) in dZ.
+ * An id outside [0, Fh) selects nothing: it is skipped on the device, never read through (the rule of tgcn_hier_xw and
+ * tgcn_rows_gather).  T is read through the caches; nothing of size N x k is formed or stored.  The backward also returns
+ *       dT[f, j] = the sum of dZ[i, j] over the rows i and slots s with cls[i, s] == f              (T's layout, stride lddt)
+ * (NULL: not wanted; it needs dZ), a grouped column sum of the finished dZ like db: the rows are cut into a fixed number of
+ * slices whose partial sums [slices, Fh, k] go to the workspace (tgcn_mlp_act_linear_cls_grad_workspace_bytes) and are
+ * added in slice order: no atomics, the same bits every run, exact zeros for a row of T that no id selects.  N == 0 gives
+ * zero db, dW and dT.  Everything else is tgcn_mlp_act_linear*'s: with T == 0 or no valid id the results are its bits.
+ * S outside {1, 2}, Fh outside [1, 128], ldcls < S, ldt < k, lddt < k, a NULL cls or T with N > 0 and dT without dZ are
+ * TGCN_E_INVALID before anything is enqueued, like the conditions above. */
+int tgcn_mlp_act_linear_cls(const float *Z, int64_t ldz, const int32_t *cls, int64_t ldcls, int S, const float *T,
+                            int64_t ldt, int Fh, const float *b, const float *W, int64_t ldw, const float *c, float *C,
+                            int64_t ldc, int64_t N, int k, int n, double p, const uint64_t *seed, int64_t mask_row0,
+                            tgcn_stream stream);
+size_t tgcn_mlp_act_linear_cls_grad_workspace_bytes(int64_t N, int k, int n, int Fh);
+int tgcn_mlp_act_linear_cls_grad(const float *Z, int64_t ldz, const int32_t *cls, int64_t ldcls, int S, const float *T,
+                                 int64_t ldt, int Fh, const float *b, const float *W, int64_t ldw, const float *G,
+                                 int64_t ldg, float *dZ, int64_t lddz, float *db, float *dT, int64_t lddt, float *dW,
+                                 int64_t lddw, int64_t N, int k, int n, double p, const uint64_t *seed, int64_t mask_row0,
+                                 void *workspace, size_t workspace_bytes, tgcn_stream stream);
+
 /* ---------------------------------------------------------------------------------------------
  * The same products with a weight that depends on the row's GROUP: the K per-label MLPs of the reference's MLP_label.py
  * as one network.  The N rows lie in grouped order: rows [row_ptr[g], row_ptr[g + 1]) belong to group g (0 <= g < K <= 128;

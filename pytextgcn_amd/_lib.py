@@ -128,7 +128,15 @@ SIGNATURES = {
     "tgcn_mlp_act_linear_grad": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                          c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_double, c_void_p,
                                          c_int64, c_void_p, c_size_t, c_void_p]),
-    "tgcn_mlp_grouped_layout_bytes": (c_size_t, [c_int, c_void_p]),
+    "tgcn_mlp_act_linear_cls": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_void_p,
+                                        c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_double,
+                                        c_void_p, c_int64, c_void_p]),
+    "tgcn_mlp_act_linear_cls_grad_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
+    "tgcn_mlp_act_linear_cls_grad": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_void_p,
+                                             c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                             c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_double, c_void_p, c_int64,
+                                             c_void_p, c_size_t, c_void_p]),
+    "tgcn_mlp_grouped_layout_bytes":(c_size_t, [c_int, c_void_p]),
     "tgcn_mlp_grouped_layout": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64,
                                         c_int64, c_int64, c_void_p, c_size_t]),
     "tgcn_mlp_grouped_act_linear": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,

@@ -51,6 +51,58 @@ __device__ __forceinline__ float act(float z, uint32_t key, uint32_t col_term, c
     return a;
 }
 
+// A bias that depends on the ROW (tgcn_mlp_act_linear_cls*): row i carries S <= 2 ids into a small table T [Fh, k], and the
+// pre-activation of (i, j) is ((Z[i, j] + T[cls[i, 0], j]) + T[cls[i, 1], j]) + b[j].  An id outside [0, Fh) selects nothing.
+// The table is read through the caches, where its at most Fh lines of a 32-column chunk stay; the products without the
+// term (CLS false) compile to what they were.
+constexpr int kClassRowsMax = 128;   // the cap on Fh (tgcn_hier_max_features has the same)
+
+struct ClassTerm {
+    const int32_t *cls;   // [N, S], row stride ldcls
+    int64_t ldcls;
+    const float *T;       // [Fh, k], row stride ldt
+    int64_t ldt;
+    int S, Fh;
+};
+
+// the ids of row i: -1 where the row selects nothing
+template <bool CLS>
+__device__ __forceinline__ void class_ids(const ClassTerm &t, int64_t i, bool live, int32_t &id0, int32_t &id1) {
+    id0 = id1 = -1;
+    if constexpr (CLS) {
+        if (live) {
+            const int32_t *row = t.cls + i * t.ldcls;
+            const int32_t a = row[0], b = t.S > 1 ? row[1] : -1;
+            id0 = (a >= 0 && a < t.Fh) ? a : -1;
+            id1 = (b >= 0 && b < t.Fh) ? b : -1;
+        }
+    }
+}
+
+// (z + T[id0, j]) + T[id1, j]; j < k is the caller's.  Without a branch (in an unrolled loop over a lane's rows the
+// compiler would keep one exec mask per row alive): an id of -1 loads from row 0, which exists, and the sum is dropped,
+// so z comes back as it was, its bits untouched.
+template <bool CLS>
+__device__ __forceinline__ float plus_class_rows(float z, const ClassTerm &t, int32_t id0, int32_t id1, int j) {
+    if constexpr (CLS) {
+        const float t0 = t.T[(id0 < 0 ? 0 : id0) * t.ldt + j];
+        z = id0 < 0 ? z : z + t0;
+        if (t.S > 1) {                                     // (uniform)
+            const float t1 = t.T[(id1 < 0 ? 0 : id1) * t.ldt + j];
+            z = id1 < 0 ? z : z + t1;
+        }
+    }
+    return z;
+}
+
+// two ids in one register (Fh <= 128): what a lane that keeps the ids of 16 rows holds
+__device__ __forceinline__ uint32_t pack_ids(int32_t id0, int32_t id1) {
+    return (static_cast<uint32_t>(id0) & 0xffffu) | (static_cast<uint32_t>(id1) << 16);
+}
+__device__ __forceinline__ int32_t packed_id(uint32_t both, int slot) {
+    return static_cast<int16_t>(slot ? both >> 16 : both & 0xffffu);
+}
+
 inline int make_row_drop(const char *fn, double p, const uint64_t *seed, int64_t mask_row0, RowDrop &d, bool &on) {
     if (!(p >= 0.0 && p < 1.0)) {
         set_error("%s: p must be in [0, 1) (p=%g)", fn, p);

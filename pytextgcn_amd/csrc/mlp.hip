@@ -7,6 +7,12 @@
 //                                dW[m, j] = sum_i G[i, m] a(i, j)                       (a recomputed, the same mask)
 // keep(i, j) is the decision of tgcn_gemm_*_dropout (drop_hash.h) for mask row mask_row0 + i, column j.
 //
+// tgcn_mlp_act_linear_cls* are the same three kernels with CLS = true: the pre-activation is then
+// ((Z[i, j] + T[cls[i, 0], j]) + T[cls[i, 1], j]) + b[j], a bias that depends on the row (ClassTerm, fused_act.h) -- the
+// one-hot class columns that MLP_level.py appends to the TF-IDF features, as rows of the first layer's weight.  Each kernel
+// adds the rows of T where it loads Z, so no N x k sum is stored; dT is a grouped column sum of the finished dZ
+// (k_mlp_class_sums), computed next to db.
+//
 // All three products run on v_mfma_f32_32x32x2_f32 (fragment maps: fused_act.h).  Z, W and G are row-major, so every
 // global load here has the lanes of a half wave on 32 consecutive floats of one row (one 128-byte run); they are plain
 // dword loads, which ask nothing of the strides or the alignment.  Where the matrix cores want an operand with the ROW
@@ -26,15 +32,16 @@ namespace {
 // Per MFMA step a lane forms ONE element a(i, j) -- its row i is fixed, so the row key of the hash is paid once per
 // lane -- and spends it on NT tiles.
 // ---------------------------------------------------------------------------------------------
-template <int NT, bool DROP>
+template <int NT, bool DROP, bool CLS>
 __global__ __launch_bounds__(256, 2) void k_mlp_fwd(const float *__restrict__ Z, int64_t ldz, const float *__restrict__ b,
                                                     const float *__restrict__ W, int64_t ldw, const float *__restrict__ cb,
                                                     float *__restrict__ C, int64_t ldc, int64_t N, int K, int n,
-                                                    const RowDrop d) {
+                                                    const RowDrop d, const ClassTerm ct) {
     constexpr int KC = 32, NP = 32 * NT, LD = KC + 1;
     __shared__ float Ws[NP * LD];
     __shared__ float Zs[128 * LD];
     __shared__ float bs[KC];
+    __shared__ int32_t cs[CLS ? 2 * 128 : 2];              // the ids of the workgroup's rows (-1: nothing selected)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, c = lane & 31;
     const int64_t blk0 = int64_t(blockIdx.x) * 128;
     const int64_t row0 = blk0 + wave * 32;
@@ -47,10 +54,13 @@ __global__ __launch_bounds__(256, 2) void k_mlp_fwd(const float *__restrict__ Z,
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    if constexpr (CLS) {
+        if (tid < 128) class_ids<CLS>(ct, blk0 + tid, blk0 + tid < N, cs[2 * tid], cs[2 * tid + 1]);
+    }
 
     for (int k0 = 0; k0 < K; k0 += KC) {
         const bool kin = k0 + skk < K;
-        __syncthreads();                                   // the previous chunk has been read
+        __syncthreads();                                   // the previous chunk has been read (and the ids are written)
 #pragma unroll 4
         for (int u = 0; u < 4 * NT; ++u) {
             const int m = sr + 8 * u;
@@ -59,7 +69,11 @@ __global__ __launch_bounds__(256, 2) void k_mlp_fwd(const float *__restrict__ Z,
 #pragma unroll
         for (int u = 0; u < 16; ++u) {
             const int r = sr + 8 * u;
-            Zs[r * LD + skk] = (kin && blk0 + r < N) ? Z[(blk0 + r) * ldz + k0 + skk] : 0.f;
+            float z = (kin && blk0 + r < N) ? Z[(blk0 + r) * ldz + k0 + skk] : 0.f;
+            if constexpr (CLS) {
+                if (kin) z = plus_class_rows<CLS>(z, ct, cs[2 * r], cs[2 * r + 1], k0 + skk);
+            }
+            Zs[r * LD + skk] = z;
         }
         if (tid < KC) bs[tid] = kin ? b[k0 + tid] : 0.f;
         __syncthreads();
@@ -94,11 +108,12 @@ __global__ __launch_bounds__(256, 2) void k_mlp_fwd(const float *__restrict__ Z,
 // launch covers (n > 128: more rows of G than a lane has registers for beside the keys) and this is not its first piece:
 // the masked, scaled partial sum is added to what dZ holds.
 // ---------------------------------------------------------------------------------------------
-template <int NT, bool DROP>
+template <int NT, bool DROP, bool CLS>
 __global__ __launch_bounds__(256, 2) void k_mlp_grad_z(const float *__restrict__ Z, int64_t ldz, const float *__restrict__ b,
                                                        const float *__restrict__ W, int64_t ldw,
                                                        const float *__restrict__ G, int64_t ldg, float *__restrict__ dZ,
-                                                       int64_t lddz, int64_t N, int K, int n, int accum, const RowDrop d) {
+                                                       int64_t lddz, int64_t N, int K, int n, int accum, const RowDrop d,
+                                                       const ClassTerm ct) {
     constexpr int NP = 32 * NT;
     __shared__ float Ws[NP * 32];
     __shared__ float Gs[4 * 32 * 33];
@@ -124,6 +139,16 @@ __global__ __launch_bounds__(256, 2) void k_mlp_grad_z(const float *__restrict__
     uint32_t keys[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) keys[r] = row_key<DROP>(d, row0 + acc_row(r, half));
+    // The ids of the workgroup's 128 rows (pack_ids), in LDS and read again for every tile: held in registers, the
+    // compiler keeps 32 row addresses of T per lane alive across the loop and the widest instantiation spills.
+    __shared__ uint32_t cs[CLS ? 128 : 1];
+    if constexpr (CLS) {
+        if (lane < 32) {
+            int32_t id0, id1;
+            class_ids<CLS>(ct, row0 + lane, row0 + lane < N, id0, id1);
+            cs[wave * 32 + lane] = pack_ids(id0, id1);
+        }
+    }
 
     for (int j0 = 0; j0 < K; j0 += 32) {
         __syncthreads();                                   // the previous tile has been read
@@ -139,6 +164,10 @@ __global__ __launch_bounds__(256, 2) void k_mlp_grad_z(const float *__restrict__
         for (int r = 0; r < 16; ++r) {
             const int64_t row = row0 + acc_row(r, half);
             z[r] = (row < N && j < K) ? Z[row * ldz + j] : 0.f;
+            if constexpr (CLS) {
+                const uint32_t ids = cs[wave * 32 + acc_row(r, half)];
+                if (j < K) z[r] = plus_class_rows<CLS>(z[r], ct, packed_id(ids, 0), packed_id(ids, 1), j);
+            }
         }
         __syncthreads();
         f32x16 acc;
@@ -170,10 +199,11 @@ __global__ __launch_bounds__(256, 2) void k_mlp_grad_z(const float *__restrict__
 // read their slab of G straight from memory, 128 bytes per half wave.  The slices' partial sums go to the workspace and
 // are added in a fixed order by k_reduce_slices.
 // ---------------------------------------------------------------------------------------------
-template <int TW, bool DROP>
+template <int TW, bool DROP, bool CLS>
 __global__ __launch_bounds__(256, 2) void k_mlp_grad_w(const float *__restrict__ Z, int64_t ldz, const float *__restrict__ b,
                                                        const float *__restrict__ G, int64_t ldg, float *__restrict__ part,
-                                                       int64_t N, int K, int n, int64_t chunks_per_slice, const RowDrop d) {
+                                                       int64_t N, int K, int n, int64_t chunks_per_slice, const RowDrop d,
+                                                       const ClassTerm ct) {
     constexpr int NP = 128 * TW;
     __shared__ float As[kWChunk * 32];
     __shared__ uint32_t ks[kWChunk];
@@ -200,6 +230,11 @@ __global__ __launch_bounds__(256, 2) void k_mlp_grad_w(const float *__restrict__
         for (int u = 0; u < 16; ++u) {
             const int64_t i = i0 + sr + 8 * u;
             z[u] = (i < i_end && j < K) ? Z[i * ldz + j] : 0.f;
+            if constexpr (CLS) {
+                int32_t id0, id1;
+                class_ids<CLS>(ct, i, i < i_end && j < K, id0, id1);
+                if (j < K) z[u] = plus_class_rows<CLS>(z[u], ct, id0, id1, j);
+            }
         }
         __syncthreads();                                   // the previous tile has been read
         if constexpr (DROP) {
@@ -236,8 +271,65 @@ __global__ __launch_bounds__(256, 2) void k_mlp_grad_w(const float *__restrict__
         for (int r = 0; r < 16; ++r) out[int64_t((wave * TW + t) * 32 + acc_row(r, half)) * kpad] = acc[t][r];
 }
 
-// the workspace: the column-sum partials of db first, the slices' partial sums of dW after them
+// ---------------------------------------------------------------------------------------------
+// dT[f, j] = the sum of dZ[i, j] over the rows i and slots s with cls[i, s] == f: a grouped column sum of the finished dZ.
+// A workgroup is ONE wave: blockIdx.x is a tile of 64 columns, blockIdx.y a slice of the rows.  It keeps a table
+// [Fh][64] of sums in LDS (dynamic: Fh x 256 bytes, at most 32 KB), lane c owning column c of it, and walks the rows of
+// its slice in order: the row's ids are the same for the whole wave, the 64 lanes load 256 consecutive bytes of dZ and
+// each adds its element to its column of the id's row.  A lane touches no other lane's sums, so there is no barrier and
+// the order of the additions is the row order; the cost does not grow with Fh (hier.hip's k_hier_class_sums, which has a
+// lane per (class, column), walks the ids once per 8 classes).  k_reduce_slices adds the slices in order.  A row of T
+// that no id selects gets exact zeros; a row whose two slots name the same id counts twice, as the sum says.
+// ---------------------------------------------------------------------------------------------
+constexpr int kSumCols = 64;
+
+__global__ __launch_bounds__(64) void k_mlp_class_sums(const float *__restrict__ dZ, int64_t lddz, const ClassTerm ct,
+                                                       int64_t N, int K, int64_t rows_per_slice, float *__restrict__ part,
+                                                       int kpad) {
+    extern __shared__ float tab[];                         // [Fh][kSumCols]
+    const int c = threadIdx.x, j = blockIdx.x * kSumCols + c;
+    const bool in = j < K;
+    for (int f = 0; f < ct.Fh; ++f) tab[f * kSumCols + c] = 0.f;
+    const int64_t i0 = int64_t(blockIdx.y) * rows_per_slice;
+    const int64_t i1 = i0 + rows_per_slice < N ? i0 + rows_per_slice : N;
+    for (int64_t i = i0; i < i1; i += 4) {
+        int32_t id0[4], id1[4];
+        float v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            class_ids<true>(ct, i + u, i + u < i1, id0[u], id1[u]);
+            id0[u] = __builtin_amdgcn_readfirstlane(id0[u]);   // (the same in every lane)
+            id1[u] = __builtin_amdgcn_readfirstlane(id1[u]);
+            v[u] = (in && (id0[u] >= 0 || id1[u] >= 0)) ? dZ[(i + u) * lddz + j] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (id0[u] >= 0) tab[id0[u] * kSumCols + c] += v[u];
+            if (id1[u] >= 0) tab[id1[u] * kSumCols + c] += v[u];
+        }
+    }
+    if (in)
+        for (int f = 0; f < ct.Fh; ++f) part[(int64_t(blockIdx.y) * ct.Fh + f) * kpad + j] = tab[f * kSumCols + c];
+}
+
+// How the rows are cut for dT: slices of at least 64 rows, at most 1024 of them and at most 4 M floats of partial sums
+// (hier.hip's class_sum_split).
+void class_sum_split(int64_t N, int K, int Fh, int64_t &slices, int64_t &rows_per_slice) {
+    const int64_t per_slice = int64_t(Fh) * ((int64_t(K) + 31) / 32 * 32);
+    const int64_t most = std::min<int64_t>(1024, std::max<int64_t>(16, (int64_t(1) << 22) / per_slice));
+    rows_per_slice = std::max<int64_t>(64, (N + most - 1) / most);
+    slices = (N + rows_per_slice - 1) / rows_per_slice;
+}
+
+// the workspace: the column-sum partials of db first, the slices' partial sums of dW after them, those of dT last
 size_t db_floats(int64_t N, int K) { return static_cast<size_t>(colsum_blocks(N)) * static_cast<size_t>(K); }
+
+size_t dt_floats(int64_t N, int K, int Fh) {
+    if (N <= 0) return 0;
+    int64_t slices, rps;
+    class_sum_split(N, K, Fh, slices, rps);
+    return static_cast<size_t>(slices * Fh * ((int64_t(K) + 31) / 32 * 32));
+}
 
 size_t dw_floats(int64_t N, int K, int n) {
     int64_t slices, cps;
@@ -247,32 +339,32 @@ size_t dw_floats(int64_t N, int K, int n) {
     return static_cast<size_t>(slices * np * kpad);
 }
 
-template <bool DROP>
+template <bool DROP, bool CLS>
 int launch_fwd(const float *Z, int64_t ldz, const float *b, const float *W, int64_t ldw, const float *cb, float *C,
-               int64_t ldc, int64_t N, int K, int n, const RowDrop &d, hipStream_t s) {
+               int64_t ldc, int64_t N, int K, int n, const RowDrop &d, const ClassTerm &ct, hipStream_t s) {
     const unsigned grid = static_cast<unsigned>((N + 127) / 128);
     for (int col0 = 0; col0 < n; col0 += kFwdGroup) {
         const int ng = std::min(n - col0, kFwdGroup), nt = (ng + 31) / 32;
         const float *cg = cb ? cb + col0 : nullptr;
         with_tiles<1, 2, 4, 8>(nt, [&](auto NT) {
-            hipLaunchKernelGGL((k_mlp_fwd<decltype(NT)::value, DROP>), dim3(grid), dim3(256), 0, s, Z, ldz, b,
-                               W + int64_t(col0) * ldw, ldw, cg, C + col0, ldc, N, K, ng, d);
+            hipLaunchKernelGGL((k_mlp_fwd<decltype(NT)::value, DROP, CLS>), dim3(grid), dim3(256), 0, s, Z, ldz, b,
+                               W + int64_t(col0) * ldw, ldw, cg, C + col0, ldc, N, K, ng, d, ct);
         });
     }
     TGCN_HIP_CHECK(hipGetLastError());
     return TGCN_OK;
 }
 
-template <bool DROP>
+template <bool DROP, bool CLS>
 int launch_grad_z(const float *Z, int64_t ldz, const float *b, const float *W, int64_t ldw, const float *G, int64_t ldg,
-                  float *dZ, int64_t lddz, float *db, int64_t N, int K, int n, const RowDrop &d, float *part,
-                  hipStream_t s) {
+                  float *dZ, int64_t lddz, float *db, int64_t N, int K, int n, const RowDrop &d, const ClassTerm &ct,
+                  float *part, hipStream_t s) {
     const unsigned grid = static_cast<unsigned>((N + 127) / 128);
     for (int col0 = 0; col0 < n; col0 += kGzGroup) {
         const int ng = std::min(n - col0, kGzGroup), nt = (ng + 31) / 32, accum = col0 > 0;
         with_tiles<1, 2, 4>(nt, [&](auto NT) {
-            hipLaunchKernelGGL((k_mlp_grad_z<decltype(NT)::value, DROP>), dim3(grid), dim3(256), 0, s, Z, ldz, b,
-                               W + int64_t(col0) * ldw, ldw, G + col0, ldg, dZ, lddz, N, K, ng, accum, d);
+            hipLaunchKernelGGL((k_mlp_grad_z<decltype(NT)::value, DROP, CLS>), dim3(grid), dim3(256), 0, s, Z, ldz, b,
+                               W + int64_t(col0) * ldw, ldw, G + col0, ldg, dZ, lddz, N, K, ng, accum, d, ct);
         });
     }
     TGCN_HIP_CHECK(hipGetLastError());
@@ -280,9 +372,23 @@ int launch_grad_z(const float *Z, int64_t ldz, const float *b, const float *W, i
     return launch_colsum(dZ, lddz, N, K, db, part, colsum_blocks(N), s);
 }
 
-template <bool DROP>
+// dT from the finished dZ: the slices' grouped column sums, then their sum in slice order
+int launch_grad_t(const float *dZ, int64_t lddz, const ClassTerm &ct, float *dT, int64_t lddt, int64_t N, int K, float *part,
+                  hipStream_t s) {
+    int64_t slices, rps;
+    class_sum_split(N, K, ct.Fh, slices, rps);
+    const int ktiles = (K + 31) / 32, kpad = ktiles * 32;
+    const dim3 grid((K + kSumCols - 1) / kSumCols, static_cast<unsigned>(slices));
+    hipLaunchKernelGGL(k_mlp_class_sums, grid, dim3(kSumCols), sizeof(float) * ct.Fh * kSumCols, s, dZ, lddz, ct, N, K, rps,
+                       part, kpad);
+    launch_reduce_slices(part, slices, int64_t(ct.Fh) * kpad, kpad, ct.Fh, K, dT, lddt, s);
+    TGCN_HIP_CHECK(hipGetLastError());
+    return TGCN_OK;
+}
+
+template <bool DROP, bool CLS>
 int launch_grad_w(const float *Z, int64_t ldz, const float *b, const float *G, int64_t ldg, float *dW, int64_t lddw,
-                  int64_t N, int K, int n, const RowDrop &d, float *part, hipStream_t s) {
+                  int64_t N, int K, int n, const RowDrop &d, const ClassTerm &ct, float *part, hipStream_t s) {
     int64_t slices, cps;
     grad_w_split(N, K, kWTarget, slices, cps);
     const int ktiles = (K + 31) / 32, kpad = ktiles * 32;
@@ -290,9 +396,11 @@ int launch_grad_w(const float *Z, int64_t ldz, const float *b, const float *G, i
         const int ng = std::min(n - m0, kWGroup);
         const dim3 grid(ktiles, static_cast<unsigned>(slices));
         if (ng > 128)
-            hipLaunchKernelGGL((k_mlp_grad_w<2, DROP>), grid, dim3(256), 0, s, Z, ldz, b, G + m0, ldg, part, N, K, ng, cps, d);
+            hipLaunchKernelGGL((k_mlp_grad_w<2, DROP, CLS>), grid, dim3(256), 0, s, Z, ldz, b, G + m0, ldg, part, N, K, ng, cps,
+                               d, ct);
         else
-            hipLaunchKernelGGL((k_mlp_grad_w<1, DROP>), grid, dim3(256), 0, s, Z, ldz, b, G + m0, ldg, part, N, K, ng, cps, d);
+            hipLaunchKernelGGL((k_mlp_grad_w<1, DROP, CLS>), grid, dim3(256), 0, s, Z, ldz, b, G + m0, ldg, part, N, K, ng, cps,
+                               d, ct);
         const int np = ng > 128 ? 256 : 128;
         launch_reduce_slices(part, slices, int64_t(np) * kpad, kpad, ng, K, dW + int64_t(m0) * lddw, lddw, s);
     }
@@ -300,16 +408,38 @@ int launch_grad_w(const float *Z, int64_t ldz, const float *b, const float *G, i
     return TGCN_OK;
 }
 
-}  // namespace
-}  // namespace tgcn
+// f(DROP, CLS) with the two switches as integral constants
+template <class F>
+int with_variant(bool drop, bool cls, F &&f) {
+    using Y = std::true_type;
+    using No = std::false_type;
+    return drop ? (cls ? f(Y{}, Y{}) : f(Y{}, No{})) : (cls ? f(No{}, Y{}) : f(No{}, No{}));
+}
 
-extern "C" {
+// the checks of the class term; `dT` / `lddt`: the backward's (nullptr in the forward)
+int check_class_term(const char *fn, const ClassTerm &ct, int64_t N, int k, const float *dT, int64_t lddt) {
+    if (ct.S != 1 && ct.S != 2) {
+        set_error("%s: S must be 1 or 2 (S=%d)", fn, ct.S);
+        return TGCN_E_INVALID;
+    }
+    if (ct.Fh < 1 || ct.Fh > kClassRowsMax) {
+        set_error("%s: Fh must be in [1, %d] (tgcn_hier_max_features) (Fh=%d)", fn, kClassRowsMax, ct.Fh);
+        return TGCN_E_INVALID;
+    }
+    TGCN_CHECK(check_ld(fn, "ldcls", ct.ldcls, ct.S));
+    TGCN_CHECK(check_ld(fn, "ldt", ct.ldt, k));
+    if (dT) TGCN_CHECK(check_ld(fn, "lddt", lddt, k));
+    if (N > 0) {
+        TGCN_CHECK(check_ptr(fn, "cls", ct.cls));
+        TGCN_CHECK(check_ptr(fn, "T", ct.T));
+    }
+    return TGCN_OK;
+}
 
-int tgcn_mlp_act_linear(const float *Z, int64_t ldz, const float *b, const float *W, int64_t ldw, const float *c, float *C,
-                        int64_t ldc, int64_t N, int k, int n, double p, const uint64_t *seed, int64_t mask_row0,
-                        tgcn_stream stream) {
-    using namespace tgcn;
-    const char *fn = "tgcn_mlp_act_linear";
+// the two entry points with and without the class term (`term` NULL: without)
+int act_linear(const char *fn, const float *Z, int64_t ldz, const ClassTerm *term, const float *b, const float *W,
+               int64_t ldw, const float *c, float *C, int64_t ldc, int64_t N, int k, int n, double p, const uint64_t *seed,
+               int64_t mask_row0, tgcn_stream stream) {
     TGCN_CHECK(check_sizes(fn, "k", N, k, n));
     RowDrop d{};
     bool drop = false;
@@ -317,27 +447,27 @@ int tgcn_mlp_act_linear(const float *Z, int64_t ldz, const float *b, const float
     TGCN_CHECK(check_ld(fn, "ldz", ldz, k));
     TGCN_CHECK(check_ld(fn, "ldw", ldw, k));
     TGCN_CHECK(check_ld(fn, "ldc", ldc, n));
+    if (term) TGCN_CHECK(check_class_term(fn, *term, N, k, nullptr, 0));
     if (N == 0) return TGCN_OK;                // (an empty tensor's pointer may be NULL)
     TGCN_CHECK(check_ptr(fn, "Z", Z));
     TGCN_CHECK(check_ptr(fn, "b", b));
     TGCN_CHECK(check_ptr(fn, "W", W));
     TGCN_CHECK(check_ptr(fn, "C", C));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return drop ? launch_fwd<true>(Z, ldz, b, W, ldw, c, C, ldc, N, k, n, d, s)
-                : launch_fwd<false>(Z, ldz, b, W, ldw, c, C, ldc, N, k, n, d, s);
+    const ClassTerm ct = term ? *term : ClassTerm{};
+    return with_variant(drop, term != nullptr, [&](auto DROP, auto CLS) {
+        return launch_fwd<decltype(DROP)::value, decltype(CLS)::value>(Z, ldz, b, W, ldw, c, C, ldc, N, k, n, d, ct, s);
+    });
 }
 
-size_t tgcn_mlp_act_linear_grad_workspace_bytes(int64_t N, int k, int n) {
-    if (N < 0 || k <= 0 || n <= 0) return 0;
-    return (tgcn::db_floats(N, k) + tgcn::dw_floats(N, k, n)) * sizeof(float);
+size_t grad_workspace_floats(int64_t N, int k, int n, int Fh) {
+    return db_floats(N, k) + dw_floats(N, k, n) + (Fh > 0 ? dt_floats(N, k, Fh) : 0);
 }
 
-int tgcn_mlp_act_linear_grad(const float *Z, int64_t ldz, const float *b, const float *W, int64_t ldw, const float *G,
-                             int64_t ldg, float *dZ, int64_t lddz, float *db, float *dW, int64_t lddw, int64_t N, int k,
-                             int n, double p, const uint64_t *seed, int64_t mask_row0, void *workspace,
-                             size_t workspace_bytes, tgcn_stream stream) {
-    using namespace tgcn;
-    const char *fn = "tgcn_mlp_act_linear_grad";
+int act_linear_grad(const char *fn, const float *Z, int64_t ldz, const ClassTerm *term, const float *b, const float *W,
+                    int64_t ldw, const float *G, int64_t ldg, float *dZ, int64_t lddz, float *db, float *dT, int64_t lddt,
+                    float *dW, int64_t lddw, int64_t N, int k, int n, double p, const uint64_t *seed, int64_t mask_row0,
+                    void *workspace, size_t workspace_bytes, tgcn_stream stream) {
     TGCN_CHECK(check_sizes(fn, "k", N, k, n));
     RowDrop d{};
     bool drop = false;
@@ -347,14 +477,20 @@ int tgcn_mlp_act_linear_grad(const float *Z, int64_t ldz, const float *b, const 
     TGCN_CHECK(check_ld(fn, "ldg", ldg, n));
     if (dZ) TGCN_CHECK(check_ld(fn, "lddz", lddz, k));
     if (dW) TGCN_CHECK(check_ld(fn, "lddw", lddw, k));
+    if (term) TGCN_CHECK(check_class_term(fn, *term, N, k, dT, lddt));
     if ((dZ == nullptr) != (db == nullptr) && N > 0) {     // (N == 0: dZ has no element and its pointer may be NULL)
         set_error("%s: dZ and db are computed together: pass both or neither (db is the column sum of dZ)", fn);
+        return TGCN_E_INVALID;
+    }
+    if (dT && !dZ && N > 0) {
+        set_error("%s: dT is requested without dZ (dT is a grouped column sum of dZ)", fn);
         return TGCN_E_INVALID;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (N == 0) {                              // empty sums; there is no element of dZ
         if (db) TGCN_HIP_CHECK(hipMemsetAsync(db, 0, sizeof(float) * k, s));
         if (dW) TGCN_HIP_CHECK(hipMemset2DAsync(dW, sizeof(float) * lddw, 0, sizeof(float) * k, n, s));
+        if (dT) TGCN_HIP_CHECK(hipMemset2DAsync(dT, sizeof(float) * lddt, 0, sizeof(float) * k, term->Fh, s));
         return TGCN_OK;
     }
     TGCN_CHECK(check_ptr(fn, "Z", Z));
@@ -365,23 +501,73 @@ int tgcn_mlp_act_linear_grad(const float *Z, int64_t ldz, const float *b, const 
         set_error("%s: dZ (with db) and dW are both NULL: nothing to compute", fn);
         return TGCN_E_INVALID;
     }
-    const size_t need = tgcn_mlp_act_linear_grad_workspace_bytes(N, k, n);
+    const size_t need = grad_workspace_floats(N, k, n, term ? term->Fh : 0) * sizeof(float);
     if (!workspace || workspace_bytes < need) {
-        set_error("%s: workspace of %zu bytes, tgcn_mlp_act_linear_grad_workspace_bytes() asks for %zu", fn,
-                  workspace ? workspace_bytes : size_t(0), need);
+        set_error("%s: workspace of %zu bytes, %s_workspace_bytes() asks for %zu", fn, workspace ? workspace_bytes : size_t(0),
+                  fn, need);
         return TGCN_E_INVALID;
     }
     float *part_b = static_cast<float *>(workspace);
     float *part_w = part_b + db_floats(N, k);
-    if (dZ) {
-        TGCN_CHECK(drop ? launch_grad_z<true>(Z, ldz, b, W, ldw, G, ldg, dZ, lddz, db, N, k, n, d, part_b, s)
-                        : launch_grad_z<false>(Z, ldz, b, W, ldw, G, ldg, dZ, lddz, db, N, k, n, d, part_b, s));
-    }
-    if (dW) {
-        TGCN_CHECK(drop ? launch_grad_w<true>(Z, ldz, b, G, ldg, dW, lddw, N, k, n, d, part_w, s)
-                        : launch_grad_w<false>(Z, ldz, b, G, ldg, dW, lddw, N, k, n, d, part_w, s));
-    }
-    return TGCN_OK;
+    float *part_t = part_w + dw_floats(N, k, n);
+    const ClassTerm ct = term ? *term : ClassTerm{};
+    return with_variant(drop, term != nullptr, [&](auto DROP, auto CLS) {
+        constexpr bool kDrop = decltype(DROP)::value, kCls = decltype(CLS)::value;
+        if (dZ) {
+            TGCN_CHECK((launch_grad_z<kDrop, kCls>(Z, ldz, b, W, ldw, G, ldg, dZ, lddz, db, N, k, n, d, ct, part_b, s)));
+            if (dT) TGCN_CHECK(launch_grad_t(dZ, lddz, ct, dT, lddt, N, k, part_t, s));
+        }
+        if (dW) TGCN_CHECK((launch_grad_w<kDrop, kCls>(Z, ldz, b, G, ldg, dW, lddw, N, k, n, d, ct, part_w, s)));
+        return int(TGCN_OK);
+    });
+}
+
+}  // namespace
+}  // namespace tgcn
+
+extern "C" {
+
+int tgcn_mlp_act_linear(const float *Z, int64_t ldz, const float *b, const float *W, int64_t ldw, const float *c, float *C,
+                        int64_t ldc, int64_t N, int k, int n, double p, const uint64_t *seed, int64_t mask_row0,
+                        tgcn_stream stream) {
+    return tgcn::act_linear("tgcn_mlp_act_linear", Z, ldz, nullptr, b, W, ldw, c, C, ldc, N, k, n, p, seed, mask_row0, stream);
+}
+
+size_t tgcn_mlp_act_linear_grad_workspace_bytes(int64_t N, int k, int n) {
+    if (N < 0 || k <= 0 || n <= 0) return 0;
+    return tgcn::grad_workspace_floats(N, k, n, 0) * sizeof(float);
+}
+
+int tgcn_mlp_act_linear_grad(const float *Z, int64_t ldz, const float *b, const float *W, int64_t ldw, const float *G,
+                             int64_t ldg, float *dZ, int64_t lddz, float *db, float *dW, int64_t lddw, int64_t N, int k,
+                             int n, double p, const uint64_t *seed, int64_t mask_row0, void *workspace,
+                             size_t workspace_bytes, tgcn_stream stream) {
+    return tgcn::act_linear_grad("tgcn_mlp_act_linear_grad", Z, ldz, nullptr, b, W, ldw, G, ldg, dZ, lddz, db, nullptr, 0, dW,
+                                 lddw, N, k, n, p, seed, mask_row0, workspace, workspace_bytes, stream);
+}
+
+int tgcn_mlp_act_linear_cls(const float *Z, int64_t ldz, const int32_t *cls, int64_t ldcls, int S, const float *T,
+                            int64_t ldt, int Fh, const float *b, const float *W, int64_t ldw, const float *c, float *C,
+                            int64_t ldc, int64_t N, int k, int n, double p, const uint64_t *seed, int64_t mask_row0,
+                            tgcn_stream stream) {
+    const tgcn::ClassTerm ct{cls, ldcls, T, ldt, S, Fh};
+    return tgcn::act_linear("tgcn_mlp_act_linear_cls", Z, ldz, &ct, b, W, ldw, c, C, ldc, N, k, n, p, seed, mask_row0, stream);
+}
+
+size_t tgcn_mlp_act_linear_cls_grad_workspace_bytes(int64_t N, int k, int n, int Fh) {
+    if (N < 0 || k <= 0 || n <= 0 || Fh < 1 || Fh > tgcn::kClassRowsMax) return 0;
+    return tgcn::grad_workspace_floats(N, k, n, Fh) * sizeof(float);
+}
+
+int tgcn_mlp_act_linear_cls_grad(const float *Z, int64_t ldz, const int32_t *cls, int64_t ldcls, int S, const float *T,
+                                 int64_t ldt, int Fh, const float *b, const float *W, int64_t ldw, const float *G,
+                                 int64_t ldg, float *dZ, int64_t lddz, float *db, float *dT, int64_t lddt, float *dW,
+                                 int64_t lddw, int64_t N, int k, int n, double p, const uint64_t *seed, int64_t mask_row0,
+                                 void *workspace, size_t workspace_bytes, tgcn_stream stream) {
+    const tgcn::ClassTerm ct{cls, ldcls, T, ldt, S, Fh};
+    return tgcn::act_linear_grad("tgcn_mlp_act_linear_cls_grad", Z, ldz, &ct, b, W, ldw, G, ldg, dZ, lddz, db, dT, lddt, dW,
+                                 lddw, N, k, n, p, seed, mask_row0, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"
+

@@ -120,6 +120,125 @@ def act_linear(Z: Tensor, b: Tensor, W: Tensor, c: Optional[Tensor] = None, p: f
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# The same product with a bias that depends on the ROW (libtgcn.so `tgcn_mlp_act_linear_cls*`): the one-hot class columns
+# that MLP_level.py appends to its features, as rows of a table T [Fh, k] picked by ids cls [N, S] (S = 1 or 2).  The
+# pre-activation is ((Z + T[cls[:, 0]]) + T[cls[:, 1]]) + b; an id outside [0, Fh) selects nothing.
+# ---------------------------------------------------------------------------------------------------------------------
+MAX_CLASS_SLOTS = 2
+
+
+def max_class_rows() -> int:
+    """The cap on the rows of T (`tgcn_hier_max_features`, 128)."""
+    return int(_lib.load().tgcn_hier_max_features())
+
+
+def _require_cls(Z: Tensor, cls: Tensor, T: Tensor) -> None:
+    if not cls.is_cuda or not T.is_cuda:
+        raise RuntimeError("pytextgcn_amd: the fused MLP product needs `cls` and `T` on an AMD GPU; there is no CPU fallback")
+    if cls.dtype != torch.int32 or T.dtype != torch.float32:
+        raise TypeError(f"act_linear_cls: `cls` must be int32 and `T` float32 (got {cls.dtype}, {T.dtype})")
+    if cls.dim() != 2 or T.dim() != 2 or cls.size(0) != Z.size(0) or T.size(1) != Z.size(1) \
+            or not 1 <= cls.size(1) <= MAX_CLASS_SLOTS or not 1 <= T.size(0) <= max_class_rows():
+        raise ValueError(f"act_linear_cls: cls {tuple(cls.shape)} (N, S in 1..{MAX_CLASS_SLOTS}) and T {tuple(T.shape)} "
+                         f"(Fh in 1..{max_class_rows()}, k) do not fit Z {tuple(Z.shape)} (N, k)")
+
+
+def _class_args(cls: Tensor, T: Tensor):
+    """(cls, T) with unit column strides and the seven arguments that describe them."""
+    cls, T = _unit_cols(cls), _unit_cols(T)
+    S, (Fh, k) = cls.size(1), T.shape
+    return cls, T, (cls.data_ptr(), max(cls.stride(0), S), S, T.data_ptr(), max(T.stride(0), k), Fh)
+
+
+def act_linear_cls_forward(Z: Tensor, b: Tensor, W: Tensor, cls: Tensor, T: Tensor, c: Optional[Tensor] = None,
+                           p: float = 0.0, seed: Optional[Tensor] = None, out: Optional[Tensor] = None,
+                           mask_row0: int = 0) -> Tensor:
+    """C [N, n] = dropout(selu(Z + T[cls[:, 0]] (+ T[cls[:, 1]]) + b), p) @ W.t() (+ c).  No autograd."""
+    lib = _lib.load()
+    _require_cls(Z, cls, T)
+    Z, W, b = _unit_cols(Z), _unit_cols(W), b.contiguous()
+    cls, T, term = _class_args(cls, T)
+    N, k = Z.shape
+    n = W.size(0)
+    C = alloc_padded(N, n, Z.device) if out is None else out
+    _lib.check(lib.tgcn_mlp_act_linear_cls(Z.data_ptr(), max(Z.stride(0), k), *term, b.data_ptr(), W.data_ptr(),
+                                           max(W.stride(0), k), c.contiguous().data_ptr() if c is not None else None,
+                                           C.data_ptr(), max(C.stride(0), n), N, k, n, float(p), _seed_ptr(seed, Z.device),
+                                           int(mask_row0), _stream_ptr(Z.device)))
+    return C
+
+
+def act_linear_cls_backward(Z: Tensor, b: Tensor, W: Tensor, cls: Tensor, T: Tensor, G: Tensor, p: float = 0.0,
+                            seed: Optional[Tensor] = None, want_z: bool = True, want_w: bool = True, want_t: bool = True,
+                            mask_row0: int = 0):
+    """(dZ, db, dW, dT) of `act_linear_cls_forward` for G = dC; what is not wanted comes back as None.  dT [Fh, k] is the
+    sum of dZ's rows per id (zero for a row of T that no id selects) and comes with dZ: `want_t` implies `want_z`."""
+    want_z = want_z or want_t
+    if not (want_z or want_w):
+        return None, None, None, None
+    lib = _lib.load()
+    _require_cls(Z, cls, T)
+    Z, W, b, G = _unit_cols(Z), _unit_cols(W), b.contiguous(), _unit_cols(G)
+    cls, T, term = _class_args(cls, T)
+    N, k = Z.shape
+    n, Fh = W.size(0), T.size(0)
+    dZ = alloc_padded(N, k, Z.device) if want_z else None
+    db = torch.empty(k, dtype=torch.float32, device=Z.device) if want_z else None
+    dT = torch.empty(Fh, k, dtype=torch.float32, device=Z.device) if want_t else None
+    dW = torch.empty(n, k, dtype=torch.float32, device=Z.device) if want_w else None
+    ws = torch.empty(max(lib.tgcn_mlp_act_linear_cls_grad_workspace_bytes(N, k, n, Fh), 16), dtype=torch.uint8,
+                     device=Z.device)
+    _lib.check(lib.tgcn_mlp_act_linear_cls_grad(Z.data_ptr(), max(Z.stride(0), k), *term, b.data_ptr(), W.data_ptr(),
+                                                max(W.stride(0), k), G.data_ptr(), max(G.stride(0), n),
+                                                dZ.data_ptr() if want_z else None, max(dZ.stride(0), k) if want_z else k,
+                                                db.data_ptr() if want_z else None, dT.data_ptr() if want_t else None, k,
+                                                dW.data_ptr() if want_w else None, k, N, k, n, float(p),
+                                                _seed_ptr(seed, Z.device), int(mask_row0), ws.data_ptr(), ws.numel(),
+                                                _stream_ptr(Z.device)))
+    return dZ, db, dW, dT
+
+
+class _ActLinearCls(torch.autograd.Function):
+    """`_ActLinear` with the class term: saves Z, b, W, cls, T and the seed."""
+
+    @staticmethod
+    def forward(ctx, Z: Tensor, b: Tensor, W: Tensor, c: Optional[Tensor], cls: Tensor, T: Tensor, p: float,
+                seed: Optional[Tensor]):
+        ctx.p = p
+        ctx.has_seed = seed is not None
+        ctx.save_for_backward(Z, b, W, cls, T, *([seed] if seed is not None else []))
+        return act_linear_cls_forward(Z.detach(), b.detach(), W.detach(), cls, T.detach(), None if c is None else c.detach(),
+                                      p, seed)
+
+    @staticmethod
+    def backward(ctx, G: Tensor):
+        Z, b, W, cls, T = ctx.saved_tensors[:5]
+        seed = ctx.saved_tensors[5] if ctx.has_seed else None
+        need = ctx.needs_input_grad
+        dZ, db, dW, dT = act_linear_cls_backward(Z, b, W, cls, T, G, ctx.p, seed, want_z=need[0] or need[1], want_w=need[2],
+                                                 want_t=need[5])
+        dc = colsum(G) if need[3] else None
+        return (dZ if need[0] else None), (db if need[1] else None), dW, dc, None, dT, None, None
+
+
+def act_linear_cls(Z: Tensor, b: Tensor, W: Tensor, c: Optional[Tensor], cls: Tensor, T: Tensor, p: float = 0.0,
+                   seed: Optional[Tensor] = None) -> Tensor:
+    """`act_linear` on the pre-activation `Z + T[cls[:, 0]] (+ T[cls[:, 1]]) + b`, with gradients for Z [N, k], b [k],
+    W [n, k], c [n] and T [Fh, k].  `cls` is int32 [N, 1] or [N, 2]; an id outside [0, Fh) selects nothing.  Dropout as in
+    `act_linear`."""
+    _require(Z, b, W, c)
+    _require_cls(Z, cls, T)
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"act_linear_cls: dropout rate {p} outside [0, 1)")
+    if p == 0.0:
+        seed = None
+    elif seed is None:
+        seed = new_seed(Z.device)
+    return _ActLinearCls.apply(Z, b, W, c, cls, T, p, seed)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # The same product with a weight per GROUP of rows (libtgcn.so `tgcn_mlp_grouped_*`, pytextgcn_amd/csrc/mlp_grouped.hip):
 # the K per-label MLPs of MLP_label.py as one network (pytextgcn_amd.perlabel.PerLabelMLP).
 # ---------------------------------------------------------------------------------------------------------------------

@@ -18,8 +18,10 @@ import torch
 from torch import nn
 
 from . import dense, embed, hier, mlp
-from .conv import GCNConv, dense_hierarchy_block, features_times, is_sparse_identity, propagate, split_identity_block
+from .conv import (GCNConv, _feature_plan, _pad_cols, dense_hierarchy_block, features_times, is_sparse_identity, propagate,
+                   split_identity_block)
 from .jk import JumpingKnowledge
+from .perlevel import AppendedFeatures
 from .plan import _require_cuda
 
 # Opt-in: the reference network has no non-linearity (models.py:22 is commented out) and dropout is the
@@ -233,6 +235,33 @@ def enable_fused_mlp(on: bool = True) -> bool:
     return was
 
 
+class _AppendedFirstLayer(torch.autograd.Function):
+    """The first Linear of an MLP on `[X | H]` features, split at column `n_base` of its weight W1 [h, F + Fh]:
+    `Z = X @ W1[:, :F].t()` on X's plan and `T = W1[:, F:].t()` [Fh, h], the table of `mlp.act_linear_cls`.  The backward
+    writes X^T @ dZ and dT into the two row ranges of ONE [F + Fh, h] buffer and returns its transpose: one gradient of
+    the weight's shape, no zero-filled halves."""
+
+    @staticmethod
+    def forward(ctx, plan, W1, n_base: int):
+        if W1.dtype != torch.float32:
+            raise TypeError("sparse features times weight: float32 weights only (MLP_level.py casts the model with .float())")
+        ctx.plan, ctx.n_base = plan, n_base
+        h = W1.size(0)
+        h4 = (h + 3) & ~3
+        w = W1.detach()
+        z = plan.spmm(_pad_cols(w[:, :n_base].t(), h4).contiguous())
+        return (z if h4 == h else z[:, :h]), w[:, n_base:].t().contiguous()
+
+    @staticmethod
+    def backward(ctx, dz, dt):
+        h, n_base = dz.size(1), ctx.n_base
+        h4 = (h + 3) & ~3
+        dwt = torch.empty(n_base + dt.size(0), h4, dtype=torch.float32, device=dz.device)
+        ctx.plan.spmm(_pad_cols(dz, h4).contiguous(), transpose=True, out=dwt[:n_base])
+        dwt[n_base:, :h] = dt
+        return None, dwt[:, :h].t(), None
+
+
 class MLP(nn.Module):
     """Drop-in for `textgcn.lib.models.MLP` (textgcn/lib/models.py:83-102), the TF-IDF bag-of-words baseline of
     MLP_flat.py / MLP_level.py / MLP_label.py: `Linear(in_channels, hidden[0])`, `Linear(hidden[i], hidden[i + 1])` ...,
@@ -250,7 +279,14 @@ class MLP(nn.Module):
     kept for the backward.  It runs in eval mode and whenever the dropout rate is 0; in training with 0 < rate < 1 only
     while `enable_fused_dropout()` is on, because the mask is then drawn from the library's random stream, not torch's
     (the rule `GCN` and `EGCN` follow).  Everything else (rate 1 in training included), and everything after
-    `enable_fused_mlp(False)`, is composed from `EmbeddingLinear`, `torch.selu` and `self.dropout`."""
+    `enable_fused_mlp(False)`, is composed from `EmbeddingLinear`, `torch.selu` and `self.dropout`.
+
+    The per-level strategy (MLP_level.py): `forward` also takes a `perlevel.AppendedFeatures`, the matrix `[X | H_1 | H_2]`
+    of `append_feats` held as the sparse X plus class ids.  On the fused path `Z1 = X @ layers[0].weight[:, :F].t()` runs
+    on X's own cached plan -- the one a level-1 model on X built -- and the class columns enter the first `mlp.act_linear_cls`
+    as a per-row bias, rows of `layers[0].weight[:, F:].t()`; the weight's gradient is one tensor of its shape.  The
+    parameters are those of `MLP(F + Fh, ...)`.  Off the fused path, with more than two blocks or more than
+    `mlp.max_class_rows()` appended columns, `forward` runs on `x.to_sparse()`."""
 
     def __init__(self, in_channels, out_channels, hidden, dropout=0.5):
         super().__init__()
@@ -270,8 +306,27 @@ class MLP(nn.Module):
             return False
         return not (self.training and p != 0.0 and not (_FUSED_DROPOUT and 0.0 < p < 1.0))
 
+    def takes_class_term(self, x) -> bool:
+        """Whether `forward` on the `perlevel.AppendedFeatures` `x` runs the class columns as a per-row bias of the first
+        fused product: on the fused path, with at most `mlp.MAX_CLASS_SLOTS` blocks of at most `mlp.max_class_rows()`
+        columns together.  Otherwise `forward` runs on `x.to_sparse()`."""
+        return (isinstance(x, AppendedFeatures) and self.takes_fused_path(x) and len(x.blocks) <= mlp.MAX_CLASS_SLOTS
+                and x.n_appended <= mlp.max_class_rows() and x.size(1) == self.layers[0].in_features)
+
     def forward(self, x):
         _require_cuda(x, "x")
+        if isinstance(x, AppendedFeatures):
+            if self.takes_class_term(x):
+                p = float(self.dropout.p) if self.training else 0.0
+                first, second, last = self.layers[0], self.layers[1], len(self.layers) - 1
+                # [X | H] @ W1.t() = X @ W1[:, :F].t() + W1[:, F:].t()[class]: the first on X's own plan, the second in the product
+                z, t = _AppendedFirstLayer.apply(_feature_plan(x.base), first.weight, x.n_base)
+                z = mlp.act_linear_cls(z, first.bias, second.weight, second.bias if last == 1 else None, x.ids, t, p)
+                for i in range(2, len(self.layers)):
+                    prev, layer = self.layers[i - 1], self.layers[i]
+                    z = mlp.act_linear(z, prev.bias, layer.weight, layer.bias if i == last else None, p)
+                return z
+            x = x.to_sparse()
         if not self.takes_fused_path(x):
             last = len(self.layers) - 1
             for i, layer in enumerate(self.layers):

@@ -413,7 +413,8 @@ class PerLabelMLP(nn.Module):
     after `enable_fused_mlp(False)`, is composed group by group from `torch.selu`, `self.dropout` and `dense.xw`.
 
     Not built: per-member early stopping (the members train in lock step), `hidden` differing between members, more than
-    128 groups, the `append_feats` form of MLP_level.py, several GPUs."""
+    128 groups, the grouped network on the appended features of MLP_level.py (`perlevel.AppendedFeatures` is `MLP`'s
+    input, not this class's), several GPUs."""
 
     def __init__(self, in_channels, class_counts, hidden, dropout=0.5):
         super().__init__()
