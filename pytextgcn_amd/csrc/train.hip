@@ -95,20 +95,33 @@ __global__ __launch_bounds__(256) void k_masked_ce(const float *__restrict__ log
                     for (int off = LPR / 2; off > 0; off >>= 1) bi = min(bi, __shfl_xor(bi, off, 64));
                     if (valid[u] && sl == 0) pred[r[u]] = bi == INT32_MAX ? 0 : bi;
                 }
-                float e[KPL], sum = 0.f;
+                // The target's term is kept out of the sum of the others: the gradient at the target is
+                // p_t - 1 = -(sum of the others) / sum, which `e_t / sum - 1.f` would round to a multiple of 2^-24 --
+                // the whole gradient row of a confident sample (p_t -> 1) is of that size or smaller.
+                float e[KPL], others = 0.f, et = 0.f;
 #pragma unroll
                 for (int k = 0; k < KPL; ++k) {
                     e[k] = on[u] ? expf(x[u][k] - m) : 0.f;   // exp(-inf) = 0 for the padding
-                    sum += e[k];
+                    if (col(k) == t[u])
+                        et = e[k];
+                    else
+                        others += e[k];
                 }
 #pragma unroll
-                for (int off = LPR / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+                for (int off = LPR / 2; off > 0; off >>= 1) others += __shfl_xor(others, off, 64);
+                {
+                    // e_t from the lane that holds the target column (0 from any lane when the target is invalid)
+                    const int tc = static_cast<int>(t[u] < 0 ? 0 : t[u] >= C ? C - 1 : t[u]);
+                    et = __shfl(et, lane - sl + (V4 ? tc / KPL : tc % LPR), 64);
+                }
+                const float sum = others + et;
                 if (on[u]) {
-                    const float lse = m + logf(sum);
-                    // the lane that holds the target logit adds the row's loss term
+                    // the lane that holds the target logit adds the row's loss term, log(sum) - (x_t - m): the
+                    // difference first, so that a row at +-1e4 does not round its loss to the spacing of fp32 there
+                    const float lsum = logf(sum);
 #pragma unroll
                     for (int k = 0; k < KPL; ++k)
-                        if (col(k) == t[u]) loss += lse - x[u][k];
+                        if (col(k) == t[u]) loss += lsum - (x[u][k] - m);
                     // a class index outside [0, C) poisons the loss instead of being dropped silently
                     // (torch raises; the Python wrapper checks the labels once per tensor)
                     if (sl == 0 && (t[u] < 0 || t[u] >= C)) loss = NAN;
@@ -120,7 +133,7 @@ __global__ __launch_bounds__(256) void k_masked_ce(const float *__restrict__ log
 #pragma unroll
                     for (int k = 0; k < KPL; ++k) {
                         const int c = col(k);
-                        d[k] = (on[u] && c < C) ? (e[k] * inv - (c == t[u] ? 1.f : 0.f)) * inv_count : 0.f;
+                        d[k] = (on[u] && c < C) ? (c == t[u] ? -(others * inv) : e[k] * inv) * inv_count : 0.f;
                         cs[k] += d[k];
                     }
                     if constexpr (V4) {
@@ -159,22 +172,25 @@ __global__ __launch_bounds__(256) void k_masked_ce(const float *__restrict__ log
                     for (int off = LPR / 2; off > 0; off >>= 1) bi = min(bi, __shfl_xor(bi, off, 64));
                     if (valid && sl == 0) pred[r] = bi == INT32_MAX ? 0 : bi;
                 }
+                // as on the register path: the target's term apart from the sum of the others, differences from the
+                // row maximum before anything is added to log(sum)
+                const int64_t t = on ? target[r] : 0;
+                const bool t_ok = on && t >= 0 && t < C;   // no read outside the row (see above)
+                const float xt = t_ok ? row[t] - m : 0.f;
                 float s = 0.f;
                 if (on)
-                    for (int c = sl; c < C; c += LPR) s += expf(row[c] - m);
+                    for (int c = sl; c < C; c += LPR)
+                        if (c != t) s += expf(row[c] - m);
 #pragma unroll
                 for (int off = LPR / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-                const float lse = m + logf(s);
-                int64_t t = 0;
-                if (on) {
-                    t = target[r];
-                    // no read outside the row: an invalid class index poisons the loss (see above)
-                    if (sl == 0) loss += (t >= 0 && t < C) ? lse - row[t] : NAN;
-                }
+                const float sum = s + (t_ok ? expf(xt) : 0.f);
+                // an invalid class index poisons the loss
+                if (on && sl == 0) loss += t_ok ? logf(sum) - xt : NAN;
                 if (dlogits != nullptr && valid) {
                     float *drow = dlogits + r * ldd;
+                    const float inv = on ? 1.f / sum : 0.f;
                     for (int c = sl; c < C; c += LPR)
-                        drow[c] = on ? (expf(row[c] - lse) - (c == t ? 1.f : 0.f)) * inv_count : 0.f;
+                        drow[c] = on ? (c == t ? -(s * inv) : expf(row[c] - m) * inv) * inv_count : 0.f;
                 }
             }
         }

@@ -916,6 +916,9 @@ def test_masked_cross_entropy_matches_torch(cuda, n, C):
     (loss * 1.0).backward()
     assert abs(loss.item() - ref.item()) < TOL * abs(ref.item()) + 1e-7
     assert rel_err(lg.grad, logits.grad) < TOL
+    ref64 = logits.detach().double().requires_grad_()                        # every row to its own scale: float64 reference
+    torch.nn.functional.cross_entropy(ref64[mask], y[mask]).backward()
+    assert row_rel_err(lg.grad, ref64.grad) < TOL
     with torch.no_grad():
         assert abs(masked_cross_entropy(lg, y.to(cuda), mask.to(cuda)).item() - ref.item()) < TOL * abs(ref.item()) + 1e-7
     big = torch.randn(n, C + 5, generator=gen).to(cuda)                      # strided logits
@@ -957,6 +960,7 @@ def test_masked_cross_entropy_leaves_the_bias_gradient(cuda, n, C, scale):
     ref = logits.cpu().double().requires_grad_()
     (torch.nn.functional.cross_entropy(ref[mask.cpu()], y.cpu()[mask.cpu()]) * scale).backward()
     assert rel_err(lg.grad, ref.grad.float()) < TOL
+    assert row_rel_err(lg.grad, ref.grad) < TOL
     assert seen["known"] is not None and seen["colsum"].data_ptr() == seen["known"].data_ptr()   # no second pass
     assert seen["colsum"].shape == (C,)
     want = ref.grad.sum(0)
@@ -1011,6 +1015,9 @@ def test_masked_cross_entropy_predictions(cuda, n, C):
     want.backward()
     assert abs(loss.item() - want.item()) < TOL * abs(want.item())
     assert rel_err(ld.grad, lr.grad) < TOL
+    lr64 = logits.double().requires_grad_()
+    torch.nn.functional.cross_entropy(lr64[mask], y[mask]).backward()
+    assert row_rel_err(ld.grad, lr64.grad) < TOL
     with torch.no_grad():
         l2, p2 = masked_cross_entropy(ld.detach(), y.to(cuda), mask.to(cuda), return_pred=True)
     assert torch.equal(p2, pred) and abs(l2.item() - want.item()) < TOL * abs(want.item())
