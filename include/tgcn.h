@@ -325,12 +325,55 @@ int tgcn_grouped_ce(const float *logits, int64_t ld, int64_t n_rows, int n_cols,
                     float *dlogits, int64_t ldd, float *dbias, int64_t *pred, void *workspace, size_t workspace_bytes,
                     tgcn_stream stream);
 
+/* tgcn_member_ce -- masked CrossEntropyLoss('mean') of K EQUAL-WIDTH members in one pass: one cell of the reference's
+ * hyper-parameter sweeps (old/h_o_train.py: len(lrs) x KFold(k) two-layer GCNs on one graph) concatenated along the class
+ * axis.  Member k owns the columns [k * seg_stride, k * seg_stride + n_classes) of logits [n_rows, >= K * seg_stride] (fp32,
+ * stride ld); n_classes <= seg_stride, the columns between are pad.  Unlike tgcn_grouped_ce, every row meets every segment:
+ *   bits   uint64 [n_rows]  row r is selected for member k where bit k is set (bits at or above K are ignored)
+ *   target int64 [n_rows]   the class in [0, n_classes), shared by the members; read only where bits[r] != 0
+ *   inv_count fp32 [K] (device) = 1 / selected rows of the member, 0 for a member with none
+ * Results (loss_k, dlogits, dbias and pred may be NULL; dbias needs dlogits):
+ *   loss    device scalar = sum over the non-empty members, in index order, of loss_k
+ *   loss_k  [K] = CrossEntropyLoss('mean')(logits[sel_k][:, seg_k], target[sel_k]), NaN for a member without a selected row
+ *   dlogits stride ldd: (softmax - one-hot) * inv_count[k] inside segment k of a selected row, exactly 0.0f in every other
+ *           segment, on every unselected row and in every pad column -- all written by the call (the buffer need not be
+ *           cleared); nothing outside [0, K * seg_stride) of a row is written
+ *   dbias   [K * seg_stride] = column sums of dlogits (exactly 0 in pad columns and in the segment of an empty member)
+ *   pred    int32 [n_rows, K]: pred[r * K + k] = the LOCAL arg-max of segment k of EVERY row (first index on ties; 0 for a
+ *           row of -inf).  Without pred, rows with bits == 0 (the word nodes) are not read.
+ * The arithmetic is tgcn_masked_ce's (the target's term apart from the sum of the others).  The 16-byte leaf applies to any
+ * n_classes when seg_stride, ld and ldd are multiples of 4 and the bases are 16-byte aligned.  Deterministic (fixed-order
+ * reductions, no atomics); only enqueues on `stream`.  TGCN_E_INVALID before anything is enqueued for K outside 1..64,
+ * n_classes < 1, seg_stride < n_classes, ld or ldd < K * seg_stride, dbias without dlogits; TGCN_E_WORKSPACE for a workspace
+ * below tgcn_member_ce_workspace_bytes. */
+size_t tgcn_member_ce_workspace_bytes(int64_t n_rows, int n_members, int n_classes);
+int tgcn_member_ce(const float *logits, int64_t ld, int64_t n_rows, int n_members, int n_classes, int seg_stride,
+                   const int64_t *target, const uint64_t *bits, const float *inv_count, float *loss, float *loss_k,
+                   float *dlogits, int64_t ldd, float *dbias, int32_t *pred, void *workspace, size_t workspace_bytes,
+                   tgcn_stream stream);
+
 /* tgcn_adam_step -- one `torch.optim.Adam(..., amsgrad=...)` update of a flat fp32 tensor
  * (flat_amazon.py:89,106), torch's single-tensor formula op for op, fused into one pass.
  * max_exp_avg_sq = NULL means amsgrad=False.  `step` is the 1-based step count AFTER increment. */
 int tgcn_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq,
                    float *max_exp_avg_sq, int64_t n, double lr, double beta1, double beta2, double eps,
                    double weight_decay, int64_t step, tgcn_stream stream);
+
+/* tgcn_adam_members -- tgcn_adam_step on a contiguous [n_rows, n_cols] tensor (a bias: n_rows = 1) whose n_cols = n_members
+ * * member_width columns are K column blocks with a learning rate each: column c takes lr_host[c / member_width] (K doubles
+ * on the HOST); everything else is tgcn_adam_step op for op, so block k after the call is bit for bit what tgcn_adam_step
+ * with lr_host[k] gives on a contiguous copy of it.  16-byte bodies where member_width and n_cols are multiples of 4, 4-byte
+ * accesses otherwise.  The capturable form advances *step_dev once and leaves lr[k] / (1 - beta1^t) in scalars_dev[k] and
+ * 1 / sqrt(1 - beta2^t) in scalars_dev[K] (K + 1 floats on the device).  n_rows * n_cols == 0 is a no-op (the capturable form
+ * still advances the step).  TGCN_E_INVALID before anything is enqueued for n_cols != K * member_width, K outside 1..64, a
+ * NULL lr_host, a negative size or buffers that are not 16-byte aligned. */
+int tgcn_adam_members(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, float *max_exp_avg_sq,
+                      int64_t n_rows, int64_t n_cols, int member_width, int n_members, const double *lr_host, double beta1,
+                      double beta2, double eps, double weight_decay, int64_t step, tgcn_stream stream);
+int tgcn_adam_members_capturable(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, float *max_exp_avg_sq,
+                                 int64_t n_rows, int64_t n_cols, int member_width, int n_members, const double *lr_host,
+                                 double beta1, double beta2, double eps, double weight_decay, int64_t *step_dev,
+                                 float *scalars_dev, tgcn_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Tall-skinny fp32 GEMMs on the matrix cores (v_mfma_f32_32x32x2_f32, exact fp32): the dense

@@ -77,6 +77,14 @@ SIGNATURES = {
     "tgcn_grouped_ce": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                 c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tgcn_member_ce_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "tgcn_member_ce": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tgcn_adam_members": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int,
+                                  c_void_p, c_double, c_double, c_double, c_double, c_int64, c_void_p]),
+    "tgcn_adam_members_capturable": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int,
+                                             c_int, c_void_p, c_double, c_double, c_double, c_double, c_void_p, c_void_p,
+                                             c_void_p]),
     "tgcn_gemm_nn": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int,
                              c_void_p]),
     "tgcn_gemm_nt": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int,

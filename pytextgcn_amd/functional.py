@@ -368,3 +368,153 @@ def grouped_masked_cross_entropy(logits: Tensor, target: Tensor, mask: Tensor, g
         return _GroupedCE.apply(logits, target, mask, group, seg, counts, return_pred, route, class_map)
     loss, loss_k, _, pred, _ = _launch_grouped(logits, target, mask, group, seg, counts, False, return_pred, route, class_map)
     return (loss, loss_k, pred) if return_pred else (loss, loss_k)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Member masked cross-entropy: the K losses of one sweep cell (old/h_o_train.py: learning rates x KFold) in one pass
+# ---------------------------------------------------------------------------------------------------------------------
+_MEMBER_STATS: dict = {}
+
+
+def _member_stats(bits: Tensor, target: Tensor, K: int, C: int, cached_only: bool = False):
+    """(selected rows per member [K] on the host, `keep` = `bits != 0` on the device) for static bits and targets:
+    one device sync per distinct (bits, target) objects and versions, as `_group_stats` does.  The same visit checks that
+    the targets of the selected rows lie in [0, C).  `cached_only` (inside a HIP-graph capture): None instead of a visit."""
+    import weakref
+    key = (id(bits), id(target), K, C)
+    versions = (bits._version, target._version)
+    hit = _MEMBER_STATS.get(key)
+    if hit is not None and hit[0]() is bits and hit[1]() is target and hit[2] == versions:
+        return hit[3], hit[4]
+    if cached_only:
+        return None
+    shifts = torch.arange(K, dtype=torch.int64, device=bits.device)
+    member = ((bits.unsqueeze(1) >> shifts) & 1).bool()                  # [N, K]
+    keep = bits != 0
+    tk = target[member.any(1)]
+    bad = (tk < 0) | (tk >= C)
+    if bool(bad.any().item()):
+        raise IndexError(f"Target {int(tk[bad][0].item())} is out of bounds for {C} classes (on a row selected by a member)")
+    counts = member.sum(0).tolist()
+    try:
+        drop = lambda _, k=key: _MEMBER_STATS.pop(k, None)
+        _MEMBER_STATS[key] = (weakref.ref(bits, drop), weakref.ref(target, drop), versions, counts, keep)
+    except TypeError:
+        pass
+    return counts, keep
+
+
+def _launch_member(logits: Tensor, target: Tensor, bits: Tensor, K: int, C: int, S: int, counts, want_grad: bool,
+                   want_pred: bool):
+    lib = _lib.load()
+    _require_cuda(logits, "logits")
+    if logits.dtype != torch.float32 or logits.dim() != 2:
+        raise TypeError("logits must be a 2-D float32 tensor")
+    n, n_cols = logits.shape
+    if not 1 <= K <= 64 or C < 1 or S < C or n_cols != K * S:
+        raise ValueError(f"member_masked_cross_entropy: logits of {n_cols} columns do not hold {K} members (1..64) of {C} "
+                         f"classes at a stride of {S} columns (n_members * seg_stride columns, seg_stride >= n_classes)")
+    if target.shape != (n,) or bits.shape != (n,):
+        raise ValueError("target and bits must have one entry per logits row")
+    if target.dtype != torch.int64 or bits.dtype != torch.int64:
+        raise TypeError("target and bits must be int64 tensors (bit k of bits[r]: row r is selected for member k)")
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    keep = None
+    if counts is None or want_grad:
+        # no sync inside a HIP-graph capture: there the counts, the range check and the zero-row mask are those of the
+        # eager warm-up step with the same `bits` and `target` objects (or the caller's `counts`)
+        stats = _member_stats(bits, target, K, C, cached_only=torch.cuda.is_current_stream_capturing())
+        if stats is not None:
+            keep = stats[1]
+            counts = stats[0] if counts is None else counts
+        elif counts is None:
+            raise RuntimeError("member_masked_cross_entropy inside a HIP-graph capture: run one eager step with the same "
+                               "`bits` and `target` tensors first, or pass `counts`")
+    if len(counts) != K:
+        raise ValueError("counts must hold one entry per member")
+    inv = _inv_counts(counts, logits.device)
+    target, bits = target.contiguous(), bits.contiguous()
+    dev = logits.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    loss_k = torch.empty(K, dtype=torch.float32, device=dev)
+    pred = torch.empty(n, K, dtype=torch.int32, device=dev) if want_pred else None
+    dlogits = dbias = None
+    if want_grad:
+        dlogits = alloc_padded(n, n_cols, dev)
+        C4 = (n_cols + 3) & ~3
+        dbias = torch.zeros(C4, dtype=torch.float32, device=dev)[:n_cols] if C4 != n_cols else \
+            torch.empty(n_cols, dtype=torch.float32, device=dev)
+    ws_bytes = lib.tgcn_member_ce_workspace_bytes(n, K, C)
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    _lib.check(lib.tgcn_member_ce(
+        logits.data_ptr(), logits.stride(0), n, K, C, S, target.data_ptr(), bits.data_ptr(), inv.data_ptr(),
+        loss.data_ptr(), loss_k.data_ptr(), ptr(dlogits), dlogits.stride(0) if want_grad else n_cols, ptr(dbias), ptr(pred),
+        ws.data_ptr(), ws.numel(), _stream_ptr(dev)))
+    return loss, loss_k, (dlogits, dbias) if want_grad else None, pred, keep
+
+
+class _MemberCE(torch.autograd.Function):
+    """Built like `_GroupedCE`: the gradient buffer is scaled in place by the incoming device scalar (single use), and the
+    backward leaves the column sums and the zero rows of the gradient for the propagate step that consumes it."""
+
+    @staticmethod
+    def forward(ctx, logits, target, bits, K, C, S, counts, want_pred):
+        loss, loss_k, grads, pred, keep = _launch_member(logits.detach(), target, bits, K, C, S, counts,
+                                                         ctx.needs_input_grad[0], want_pred)
+        ctx.save_for_backward(*(grads if grads is not None else ()))
+        ctx.keep = keep
+        ctx.versions = (bits, bits._version)
+        if not want_pred:
+            ctx.mark_non_differentiable(loss_k)
+            return loss, loss_k
+        ctx.mark_non_differentiable(loss_k, pred)
+        return loss, loss_k, pred
+
+    @staticmethod
+    def backward(ctx, grad_out: Tensor, *_):
+        if getattr(ctx, "_tgcn_used", False):
+            raise RuntimeError("member_masked_cross_entropy: backward was already run through this loss (its gradient "
+                               "buffer is scaled in place); recompute the loss instead of retain_graph=True")
+        ctx._tgcn_used = True
+        dlogits, dbias = ctx.saved_tensors
+        base = padded_base(dlogits, (dlogits.size(1) + 3) & ~3)
+        if grad_out.is_cuda and grad_out.dtype == torch.float32 and grad_out.numel() == 1:
+            _scale_by_device_scalar(base if base is not None else dlogits, grad_out)
+            _scale_by_device_scalar(dbias, grad_out)
+        else:
+            dlogits.mul_(grad_out)
+            dbias.mul_(grad_out)
+        if base is not None:
+            note_colsum(base, torch.as_strided(dbias, (base.size(1),), (1,)))
+        else:
+            note_colsum(dlogits, dbias)
+        # rows with bits == 0 are exactly zero -- true for the bits of the forward pass only
+        bits, bv = ctx.versions
+        if ctx.keep is not None and bits._version == bv:
+            note_zero_rows(base if base is not None else dlogits, ctx.keep)
+        return (dlogits,) + (None,) * 7
+
+
+def member_masked_cross_entropy(logits: Tensor, target: Tensor, bits: Tensor, n_members: int, n_classes: int,
+                                seg_stride: int, counts=None, return_pred: bool = False):
+    """The K losses of one cell of the reference's sweeps (old/h_o_train.py: every learning rate x every fold of KFold trains
+    its own two-layer GCN on the same graph) on the concatenated logits of the K members, as ONE HIP kernel (libtgcn.so
+    `tgcn_member_ce`).
+
+    Member k owns the columns `[k * seg_stride, k * seg_stride + n_classes)` of `logits` [N, n_members * seg_stride] and
+    selects row r where bit k of `bits[r]` (int64, `crossval.member_bits` / `fold_bits`) is set; `target` (int64 [N]) is
+    shared by the members and read where `bits[r] != 0`.  Returns `(loss, loss_k)`: `loss_k[k] =
+    CrossEntropyLoss('mean')(logits[sel_k][:, seg_k], target[sel_k])` (NaN for a member without a selected row) and `loss` =
+    the sum of the others -- the objective whose gradient is the K separate trainings' gradients side by side.  `loss`
+    carries the gradient; `loss_k` is for reporting.
+
+    `counts`: the selected rows per member when the caller knows them (default: counted once per bits / target object, with
+    the range check of the targets; never inside a HIP-graph capture).  `return_pred=True` adds `pred` (int32 [N, K]): the
+    local arg-max of every member on EVERY row, first index on ties."""
+    K, C, S = int(n_members), int(n_classes), int(seg_stride)
+    if logits.requires_grad and torch.is_grad_enabled():
+        return _MemberCE.apply(logits, target, bits, K, C, S, counts, return_pred)
+    loss, loss_k, _, pred, _ = _launch_member(logits, target, bits, K, C, S, counts, False, return_pred)
+    return (loss, loss_k, pred) if return_pred else (loss, loss_k)
