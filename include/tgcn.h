@@ -652,6 +652,51 @@ int tgcn_mlp_grouped_act_linear_grad(const float *Z, int64_t ldz, const float *b
                                      int64_t mask_row0, void *workspace, size_t workspace_bytes, tgcn_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The layer-2 products of the grouped GCNs (PerLabelGCN, CrossValGCN) for all K members at once, with a dropout rate and a
+ * seed PER MEMBER.  Additive to ABI 7.  X [N, K h] (row stride ldx >= K h) is the concatenated hidden activation: member k
+ * owns columns [k h, (k + 1) h).  W [h, n_cols] (ldw >= n_cols) holds W_k in the column segment [col0[k], col0[k] + n[k]);
+ * the segments increase and do not overlap, pad columns may lie between, before and behind them.  C and G are [N, n_cols]
+ * (ldc, ldg >= n_cols).  Member k has a rate p[k] in [0, 1) (0: everything is kept at scale 1) and the 64-bit seed
+ * seeds[k] (DEVICE array of K, read by the kernels; seeds == NULL: no member drops anything, the eval product).  With
+ * s_k = 1 / (1 - p[k]), keep_k(i, j) the decision of tgcn_gemm_*_dropout's hash for seeds[k], mask row mask_row0 + i and
+ * column j INSIDE the member's block at the threshold of p[k], and a(i, j) = s_k keep_k(i, j) X[i, k h + j]:
+ *   tgcn_blockdiag_xw        C[i, col0[k] + m]  = sum_j a(i, j) W[j, col0[k] + m]                       m < n[k]
+ *                            every column of C that belongs to no segment is written as 0.0f: no zero fill by the caller
+ *   tgcn_blockdiag_xw_grad   dX[i, k h + j]     = s_k keep_k(i, j) sum_m G[i, col0[k] + m] W[j, col0[k] + m]
+ *                            colsum[k h + j]    = the column sums of the dX that is stored (colsum [K h])
+ *                            dW[j, col0[k] + m] = sum_i a(i, j) G[i, col0[k] + m]; pad columns of dW are 0.0f
+ *   dX and colsum together or neither, dW on its own (NULL = not wanted).  These are the decisions and, in exact
+ *   arithmetic, the values of K calls of tgcn_gemm_nn_dropout / _nt_ / _tn_ on the members' slices; the sums run in
+ *   another order, so the bits differ.  The mask is regenerated from the seed in all three products.
+ * The member table reaches the kernels as a BLOB, like tgcn_mlp_grouped_layout: tgcn_blockdiag_layout (HOST only: no device
+ * is touched, nothing is enqueued) validates the description and fills `out` (tgcn_blockdiag_layout_bytes(K) bytes; 0 for K
+ * outside [1, 128]); the caller copies the blob to the device once and passes BOTH copies (`layout_host` is read during the
+ * call, `layout_dev` by the kernels).  The rates are part of the blob (p == NULL: all 0).  The products only enqueue on
+ * `stream`: no allocation, no copy, no synchronisation, legal under HIP-graph capture.  v_mfma_f32_32x32x2_f32 (exact
+ * fp32); fixed-order reductions through `workspace` (tgcn_blockdiag_xw_grad_workspace_bytes(layout_host, N) bytes), no
+ * atomics, the same bits every run.  The launch count depends on max n[k] (column groups of 256 forward, 128 in dX and dW),
+ * never on K; X and G are read once per product and column group.  Operands: float32, unit column stride, any row stride
+ * at or above the width, 4-byte alignment (plain dword accesses: no padding or 16-byte rows are asked for).
+ * TGCN_E_INVALID before anything is enqueued: in tgcn_blockdiag_layout K outside [1, 128], h outside [1,
+ * tgcn_blockdiag_max_hidden()] (256: one workgroup of dW holds all h rows of a member's dW), n[k] < 1, a segment that
+ * starts before the end of the one before it or ends past n_cols, p[k] outside [0, 1), a short `out`; in the products a
+ * blob that is not a layout, N < 0 or N > 128 * (2^24 - 1) (the row tiles are one grid dimension), mask_row0 < 0, a leading dimension below the width, NULL operands with N > 0, dX
+ * without colsum (or the reverse), nothing wanted.  A short workspace is TGCN_E_WORKSPACE.  N == 0 is legal: C gets no row,
+ * dW and colsum are exact zeros. */
+int tgcn_blockdiag_max_hidden(void);
+size_t tgcn_blockdiag_layout_bytes(int K);
+int tgcn_blockdiag_layout(int K, int h, int64_t n_cols, const int32_t *col0, const int32_t *n, const double *p, void *out,
+                          size_t out_bytes);
+int tgcn_blockdiag_xw(const float *X, int64_t ldx, const float *W, int64_t ldw, float *C, int64_t ldc, int64_t N,
+                      const void *layout_host, const void *layout_dev, const uint64_t *seeds, int64_t mask_row0,
+                      tgcn_stream stream);
+size_t tgcn_blockdiag_xw_grad_workspace_bytes(const void *layout_host, int64_t N);
+int tgcn_blockdiag_xw_grad(const float *X, int64_t ldx, const float *W, int64_t ldw, const float *G, int64_t ldg, float *dX,
+                           int64_t lddx, float *colsum, float *dW, int64_t lddw, int64_t N, const void *layout_host,
+                           const void *layout_dev, const uint64_t *seeds, int64_t mask_row0, void *workspace,
+                           size_t workspace_bytes, tgcn_stream stream);
+
+/* ---------------------------------------------------------------------------------------------
  * JumpingKnowledge(mode="lstm") of the reference's JumpingKnowledgeNetwork (textgcn/lib/models.py:64,75; PyG 1.6.3): a
  * bidirectional LSTM of hidden width H over the L per-layer activations x_t [N, C] of every node, a Linear(2 H -> 1) on
  * [h_fwd_t | h_bwd_t], a softmax over the layers and the weighted sum

@@ -153,6 +153,15 @@ SIGNATURES = {
     "tgcn_mlp_grouped_act_linear_grad": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                                  c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p,
                                                  c_void_p, c_double, c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
+    "tgcn_blockdiag_max_hidden": (c_int, []),
+    "tgcn_blockdiag_layout_bytes": (c_size_t, [c_int]),
+    "tgcn_blockdiag_layout": (c_int, [c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "tgcn_blockdiag_xw": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
+                                  c_void_p, c_int64, c_void_p]),
+    "tgcn_blockdiag_xw_grad_workspace_bytes": (c_size_t, [c_void_p, c_int64]),
+    "tgcn_blockdiag_xw_grad": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                       c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_size_t,
+                                       c_void_p]),
     "tgcn_jk_lstm_forward_supported": (c_int, [c_int]),
     "tgcn_jk_lstm_forward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_int64, c_int64, c_void_p,
                                      c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p]),

@@ -12,7 +12,8 @@ labels and the class count.  So the K trainings are, in exact arithmetic, one tr
 
 A document is a training row of k - 1 folds and a validation row of the remaining one, so the rows of a member are a BIT of
 an int64 per node (`member_bits`, `fold_bits`) instead of the one group per row the per-label strategy has.  The dropout
-rate stays the sweep's outer loop: it is one number per network.
+rate is one more axis of the members: `CrossValGCN(dropout=[...])` takes a rate per member, so the whole grid of one graph
+-- `len(dropouts) x len(lrs) x k_split` members, `grid_members` lays them out -- trains as one network.
 """
 from __future__ import annotations
 
@@ -86,6 +87,21 @@ def fold_bits(doc_rows, folds, n_nodes: int, n_repeats: int = 1):
     return torch.from_numpy(train.view(np.int64)), torch.from_numpy(val.view(np.int64))
 
 
+def grid_members(lrs: Sequence[float], dropouts: Sequence[float], n_folds: int):
+    """`(member_lrs, member_dropouts)` of the whole grid of one graph: two lists of `len(dropouts) * len(lrs) * n_folds`
+    entries.  Member `(d * len(lrs) + l) * n_folds + f` belongs to dropout d, rate l and fold f -- the order in which
+    `fold_bits(..., n_repeats=len(dropouts) * len(lrs))` lays the folds out."""
+    lrs, dropouts, k = [float(v) for v in lrs], [float(v) for v in dropouts], int(n_folds)
+    if not lrs or not dropouts or k < 1:
+        raise ValueError("grid_members: need at least one learning rate, one dropout value and one fold")
+    if len(dropouts) * len(lrs) * k > MAX_MEMBERS:
+        raise ValueError(f"grid_members: {len(dropouts)} dropout values x {len(lrs)} rates x {k} folds are more than "
+                         f"{MAX_MEMBERS} members")
+    member_lrs = [lr for _ in dropouts for lr in lrs for _ in range(k)]
+    member_dropouts = [p for p in dropouts for _ in lrs for _ in range(k)]
+    return member_lrs, member_dropouts
+
+
 class CrossValGCN(PerLabelGCN):
     """K two-layer `GCN(in_channels, out_channels, n_hidden_gcn=h, dropout=...)` of one sweep cell as one network: a
     `PerLabelGCN` with `class_counts = [out_channels] * n_members` (its layers, `forward(g, rows=None)`, fused dropout under
@@ -93,7 +109,8 @@ class CrossValGCN(PerLabelGCN):
     layer 1 and the segment [k S, k S + C) of layer 2, S = `seg_stride` = C rounded up to 4.
 
     `loss` / `evaluate` take the members' rows as bits (`member_bits`, `fold_bits`); `MemberAdam` gives every member its own
-    learning rate.  Out of scope: a dropout rate per member, `n_gcn != 2`, an activation, `ShardedGCN`."""
+    learning rate; `dropout` is a float or one rate per member (`PerLabelGCN`).  Out of scope: `n_gcn != 2`, an activation,
+    `ShardedGCN`."""
 
     def __init__(self, in_channels, out_channels, n_members, n_hidden_gcn=64, dropout=0.5):
         K = int(n_members)
@@ -132,8 +149,10 @@ class CrossValGCN(PerLabelGCN):
         return loss_k, pred
 
     @classmethod
-    def from_members(cls, members: Sequence[nn.Module], dropout: Optional[float] = None) -> "CrossValGCN":
-        """One network from K two-layer `GCN`s of equal input, hidden and class width.  Parameters are copied."""
+    def from_members(cls, members: Sequence[nn.Module], dropout=None) -> "CrossValGCN":
+        """One network from K two-layer `GCN`s of equal input, hidden and class width.  Parameters are copied.  `dropout`
+        (a float or K floats) overrides the members' rates; without it the network keeps one float when the members'
+        rates are all equal and the K rates when they differ."""
         members = list(members)
         if not members:
             raise ValueError("from_members: no member")
@@ -146,8 +165,7 @@ class CrossValGCN(PerLabelGCN):
         if any(layer.bias is None for m in members for layer in m.layers):
             raise ValueError("from_members: members must carry biases")
         h, C = w1.size(1), w2.size(1)
-        net = cls(w1.size(0), C, len(members), n_hidden_gcn=h,
-                  dropout=members[0].dropout if dropout is None else dropout).to(w1.device)
+        net = cls(w1.size(0), C, len(members), n_hidden_gcn=h, dropout=cls._rates_of(members, dropout)).to(w1.device)
         first, second = net.layers
         with torch.no_grad():
             second.weight.zero_()

@@ -18,15 +18,16 @@ ordinary `GCN` modules the reference's scripts save and load.
 from __future__ import annotations
 
 import math
+import weakref
 from typing import List, Optional, Sequence
 
 import numpy as np
 import torch
 from torch import Tensor, nn
 
-from . import dense, functional, mlp, models
+from . import _lib, dense, functional, mlp, models
 from .conv import GCNConv, features_times, propagate
-from .plan import _require_cuda, note_colsum
+from .plan import _require_cuda, _stream_ptr, note_colsum
 
 
 def relabel(y_nodes, top_nodes, select):
@@ -91,8 +92,9 @@ class _BlockDiagXW(torch.autograd.Function):
     `dense.xw_dropout(Hcat[:, slice k], W_k, p, seeds[k])`: the same kernels, the same hash, the same bits."""
 
     @staticmethod
-    def forward(ctx, x: Tensor, w: Tensor, starts, widths, p: float, seeds: Optional[Tensor]):
+    def forward(ctx, x: Tensor, w: Tensor, starts, widths, p, seeds: Optional[Tensor]):
         K, h = len(starts), w.size(0)
+        rates = p if isinstance(p, tuple) else (p,) * K       # a rate per member; a member at rate 0 runs the plain product
         N = x.size(0)
         xd, wd = x.detach(), w.detach()
         out = torch.zeros(N, w.size(1), dtype=torch.float32, device=x.device)       # class width; pad columns stay zero
@@ -100,14 +102,16 @@ class _BlockDiagXW(torch.autograd.Function):
         masks = []
         for k, (s, c) in enumerate(zip(starts, widths)):
             a, b, o = xd[:, k * h:(k + 1) * h], wd[:, s:s + c], out[:, s:s + c]
-            if seeds is None:
+            if seeds is None or rates[k] == 0.0:
                 dense.gemm_nn(a, b, out=o)
+                masks.append(None)
             elif want_mask:
-                masks.append(dense.gemm_nn(a, b, p, seeds[k:k + 1], record_mask=True, out=o)[1])
+                masks.append(dense.gemm_nn(a, b, rates[k], seeds[k:k + 1], record_mask=True, out=o)[1])
             else:
-                dense.gemm_nn(a, b, p, seeds[k:k + 1], out=o)
-        ctx.starts, ctx.widths, ctx.p = starts, widths, p
-        ctx.has_seeds, ctx.n_masks = seeds is not None, len(masks)
+                dense.gemm_nn(a, b, rates[k], seeds[k:k + 1], out=o)
+                masks.append(None)
+        ctx.starts, ctx.widths, ctx.rates = starts, widths, rates
+        ctx.has_seeds = seeds is not None
         ctx.mask_none = [m is None for m in masks]
         ctx.save_for_backward(x, w, *([seeds] if seeds is not None else []), *[m for m in masks if m is not None])
         return out
@@ -117,8 +121,8 @@ class _BlockDiagXW(torch.autograd.Function):
         x, w = ctx.saved_tensors[:2]
         rest = list(ctx.saved_tensors[2:])
         seeds = rest.pop(0) if ctx.has_seeds else None
-        masks = [None if none else rest.pop(0) for none in ctx.mask_none] if ctx.n_masks else [None] * len(ctx.starts)
-        h, p = w.size(0), ctx.p
+        masks = [None if none else rest.pop(0) for none in ctx.mask_none]
+        h, rates = w.size(0), ctx.rates
         if g.stride(1) != 1:
             g = g.contiguous()
         dx = dw = None
@@ -129,7 +133,8 @@ class _BlockDiagXW(torch.autograd.Function):
             dw = torch.zeros_like(w, memory_format=torch.contiguous_format)           # (pad columns: exactly zero)
         for k, (s, c) in enumerate(zip(ctx.starts, ctx.widths)):
             a, b, gk = x[:, k * h:(k + 1) * h], w[:, s:s + c], g[:, s:s + c]
-            seed = None if seeds is None else seeds[k:k + 1]
+            p = rates[k]
+            seed = None if seeds is None or p == 0.0 else seeds[k:k + 1]
             if dx is not None:                 # g_k W_k^T (masked and scaled under dropout) and its column sums
                 dense.gemm_nt(gk, b, p, seed, note_colsums=True, mask=masks[k], out=dx[:, k * h:(k + 1) * h],
                               sums_out=sums[k * h:(k + 1) * h])
@@ -140,21 +145,170 @@ class _BlockDiagXW(torch.autograd.Function):
         return dx, dw, None, None, None, None
 
 
-def block_diag_xw(x: Tensor, w: Tensor, starts, widths, p: float = 0.0, seeds: Optional[Tensor] = None) -> Tensor:
+_FUSED_BLOCK_DIAG = False
+
+
+def enable_fused_block_diag(on: bool = True) -> bool:
+    """Route `block_diag_xw` through the one-launch products of all K members (`tgcn_blockdiag_xw`, `_grad`) instead of K
+    launches per product; returns the previous setting.  Off by default: the mask decisions are the same, but the sums run
+    in another order than `dense.xw_dropout`'s, so the bits are not those of the K separate members."""
+    global _FUSED_BLOCK_DIAG
+    was, _FUSED_BLOCK_DIAG = _FUSED_BLOCK_DIAG, bool(on)
+    return was
+
+
+class BlockDiagLayout:
+    """The member table of the one-launch products: segment k is columns [starts[k], starts[k] + widths[k]) of the
+    [h, n_cols] weight, `rates[k]` its dropout rate.  Built and validated on the HOST by `tgcn_blockdiag_layout` (a
+    ValueError names what does not fit; no GPU is touched); `host` is the blob as a uint8 array, `dev` its copy on `device`
+    (None: host only), uploaded once."""
+
+    HEADER = ("magic", "bytes", "K", "h", "n_cols", "n_max", "own_max", "any_drop")
+    MEMBER = np.dtype([("col0", "<i4"), ("n", "<i4"), ("own0", "<i4"), ("own1", "<i4"), ("thresh", "<u4"), ("scale", "<f4"),
+                       ("drop", "<i4"), ("pad", "<i4")])
+
+    def __init__(self, starts: Sequence[int], widths: Sequence[int], h: int, n_cols: int, rates=None, device=None):
+        lib = _lib.load()
+        K = len(starts)
+        col0 = np.ascontiguousarray(np.asarray(starts, dtype=np.int32))
+        n = np.ascontiguousarray(np.asarray(widths, dtype=np.int32))
+        p = None if rates is None else np.ascontiguousarray(np.asarray(rates, dtype=np.float64))
+        if n.shape != (K,) or (p is not None and p.shape != (K,)):
+            raise ValueError(f"BlockDiagLayout: widths and rates need one entry per member (K = {K})")
+        size = lib.tgcn_blockdiag_layout_bytes(K)
+        self.host = np.zeros(max(size, 8), dtype=np.uint8)
+        _lib.check(lib.tgcn_blockdiag_layout(K, int(h), int(n_cols), col0.ctypes.data, n.ctypes.data,
+                                             None if p is None else p.ctypes.data, self.host.ctypes.data, size))
+        self.header = dict(zip(self.HEADER, np.frombuffer(self.host, dtype="<i8", count=len(self.HEADER)).tolist()))
+        self.K, self.h, self.n_cols = K, int(h), int(n_cols)
+        self.dev = None if device is None else torch.from_numpy(self.host).to(device)
+
+    def members(self):
+        """The member table of the blob as a numpy record array (a view of `host`)."""
+        return np.frombuffer(self.host, dtype=self.MEMBER, count=self.K, offset=8 * len(self.HEADER))
+
+
+_BD_LAYOUTS: dict = {}            # id(weight) -> (weak reference to the weight, {description: BlockDiagLayout})
+
+
+def _bd_layout(w: Tensor, starts, widths, rates) -> BlockDiagLayout:
+    """The layout of the product with the weight `w`, kept for as long as `w` lives -- for a network, its layer-2
+    parameter: built in the first, eager step, found by a captured one, and NEVER evicted while the network exists (a
+    captured graph holds the raw pointer of the device blob; freeing the blob under it would hand a replay a foreign
+    member table).  An entry goes when its weight is collected."""
+    key = id(w)
+    hit = _BD_LAYOUTS.get(key)
+    if hit is None or hit[0]() is not w:
+        hit = _BD_LAYOUTS[key] = (weakref.ref(w, lambda _, k=key: _BD_LAYOUTS.pop(k, None)), {})
+    what = (starts, widths, w.size(0), w.size(1), rates, w.device)
+    layout = hit[1].get(what)
+    if layout is None:
+        layout = hit[1][what] = BlockDiagLayout(starts, widths, w.size(0), w.size(1), rates, w.device)
+    return layout
+
+
+def _ld(t: Tensor) -> int:
+    return max(t.stride(0), t.size(1))
+
+
+def _rows_cols(t: Tensor) -> Tensor:
+    return t if (t.stride(1) == 1 and (t.size(0) <= 1 or t.stride(0) >= t.size(1))) else t.contiguous()
+
+
+def block_diag_forward(x: Tensor, w: Tensor, layout: BlockDiagLayout, seeds: Optional[Tensor] = None, mask_row0: int = 0,
+                       out: Optional[Tensor] = None) -> Tensor:
+    """C [N, n_cols] of `tgcn_blockdiag_xw`: one launch per 256 columns of the widest segment for all K members; pad
+    columns are written as zeros.  `seeds` None: no member drops anything.  No autograd."""
+    lib = _lib.load()
+    x, w = _rows_cols(x), _rows_cols(w)
+    N = x.size(0)
+    c = torch.empty(N, layout.n_cols, dtype=torch.float32, device=x.device) if out is None else out
+    _lib.check(lib.tgcn_blockdiag_xw(x.data_ptr(), _ld(x), w.data_ptr(), _ld(w), c.data_ptr(), _ld(c), N,
+                                     layout.host.ctypes.data, layout.dev.data_ptr(),
+                                     None if seeds is None else seeds.data_ptr(), int(mask_row0), _stream_ptr(x.device)))
+    return c
+
+
+def block_diag_backward(x: Tensor, w: Tensor, g: Tensor, layout: BlockDiagLayout, seeds: Optional[Tensor] = None,
+                        want_x: bool = True, want_w: bool = True, mask_row0: int = 0):
+    """(dX, colsum, dW) of `tgcn_blockdiag_xw_grad` for G = dC; what is not wanted comes back as None."""
+    if not (want_x or want_w):
+        return None, None, None
+    lib = _lib.load()
+    x, w, g = _rows_cols(x), _rows_cols(w), _rows_cols(g)
+    N, dev = x.size(0), x.device
+    dx = torch.empty(N, x.size(1), dtype=torch.float32, device=dev) if want_x else None
+    sums = torch.empty(x.size(1), dtype=torch.float32, device=dev) if want_x else None
+    dw = torch.empty(w.size(0), w.size(1), dtype=torch.float32, device=dev) if want_w else None
+    need = lib.tgcn_blockdiag_xw_grad_workspace_bytes(layout.host.ctypes.data, N)
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    _lib.check(lib.tgcn_blockdiag_xw_grad(
+        x.data_ptr(), _ld(x), w.data_ptr(), _ld(w), g.data_ptr(), _ld(g), dx.data_ptr() if want_x else None,
+        _ld(dx) if want_x else x.size(1), sums.data_ptr() if want_x else None, dw.data_ptr() if want_w else None,
+        _ld(dw) if want_w else w.size(1), N, layout.host.ctypes.data, layout.dev.data_ptr(),
+        None if seeds is None else seeds.data_ptr(), int(mask_row0), ws.data_ptr(), ws.numel(), _stream_ptr(dev)))
+    return dx, sums, dw
+
+
+class _FusedBlockDiagXW(torch.autograd.Function):
+    """`_BlockDiagXW` on the one-launch products: ONE kernel per product for all K members (a launch more per 256 / 128
+    columns of the widest segment), a rate and a seed per member, the mask regenerated from the seeds in all three."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, w: Tensor, layout: BlockDiagLayout, seeds: Optional[Tensor]):
+        ctx.layout = layout
+        ctx.save_for_backward(x, w, *([seeds] if seeds is not None else []))
+        return block_diag_forward(x.detach(), w.detach(), layout, seeds)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        x, w = ctx.saved_tensors[:2]
+        seeds = ctx.saved_tensors[2] if len(ctx.saved_tensors) > 2 else None
+        dx, sums, dw = block_diag_backward(x, w, g, ctx.layout, seeds, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        if dx is not None:
+            note_colsum(dx, sums)              # the bias gradient of layer 1, ready for its propagate step
+        return dx, dw, None, None
+
+
+def member_rates(dropout, K: int, what: str = "dropout"):
+    """`dropout` as the networks keep it: a float as it is, K rates as a tuple of K floats, each in [0, 1)."""
+    if isinstance(dropout, (int, float)):
+        return dropout
+    rates = tuple(float(v) for v in dropout)
+    if len(rates) != K:
+        raise ValueError(f"{what}: {len(rates)} rates for {K} members")
+    if not all(0.0 <= v < 1.0 for v in rates):
+        raise ValueError(f"{what}: every member's rate must be in [0, 1), got {list(rates)}")
+    return rates
+
+
+def block_diag_xw(x: Tensor, w: Tensor, starts, widths, p=0.0, seeds: Optional[Tensor] = None) -> Tensor:
     """`x [N, K h] @ blockdiag(w[:, seg_1] .. w[:, seg_K])` -> [N, n_cols] (see `_BlockDiagXW`); `seeds` (int64 [K] on the
-    device) with 0 < p < 1 fuses dropout(x, p) into product k under seed k."""
+    device) with 0 < p < 1 fuses dropout(x, p) into product k under seed k.  `p` may also be K rates in [0, 1), at least
+    one of them > 0: member k drops at `p[k]` (a member at rate 0 runs the plain product).  After
+    `enable_fused_block_diag()` the three products are one launch each for all K members (`_FusedBlockDiagXW`)."""
     _require_cuda(x, "x")
     K, h = len(starts), w.size(0)
     if x.dim() != 2 or w.dim() != 2 or x.size(1) != K * h or x.dtype != torch.float32 or w.dtype != torch.float32:
         raise ValueError(f"block_diag_xw: x {tuple(x.shape)} does not fit {K} blocks of {h} rows")
     if any(s % 4 or s + c > w.size(1) for s, c in zip(starts, widths)):
         raise ValueError("block_diag_xw: segments start at multiples of 4 columns inside w")
+    p = float(p) if isinstance(p, (int, float)) else member_rates(p, K, "block_diag_xw")
     if seeds is not None:
-        if not 0.0 < p < 1.0:
+        if isinstance(p, tuple):
+            if not max(p) > 0.0:
+                raise ValueError("block_diag_xw: seeds go with at least one rate > 0")
+        elif not 0.0 < p < 1.0:
             raise ValueError("block_diag_xw: seeds go with 0 < p < 1")
         if seeds.dtype != torch.int64 or seeds.shape != (K,) or seeds.device != x.device:
             raise TypeError("block_diag_xw: seeds must be an int64 [K] tensor on the operand's device")
-    return _BlockDiagXW.apply(x, w, tuple(starts), tuple(widths), float(p), seeds)
+    if _FUSED_BLOCK_DIAG:
+        rates = None if seeds is None else (p if isinstance(p, tuple) else (p,) * K)
+        if w.device != x.device:
+            raise RuntimeError(f"block_diag_xw: x lives on {x.device}, w on {w.device}")
+        layout = _bd_layout(w, tuple(starts), tuple(widths), rates)
+        return _FusedBlockDiagXW.apply(x, w, layout, seeds)
+    return _BlockDiagXW.apply(x, w, tuple(starts), tuple(widths), p, seeds)
 
 
 class BlockDiagonalConv(nn.Module):
@@ -186,7 +340,8 @@ class BlockDiagonalConv(nn.Module):
 
 class PerLabelGCN(nn.Module):
     """The K two-layer `GCN(in_channels, C_k, n_hidden_gcn=h, dropout=...)` of perlabel_amazon.py:113 as one network
-    (module docstring).  `n_gcn` other than 2, an activation and `ShardedGCN` are out of scope.
+    (module docstring).  `n_gcn` other than 2, an activation and `ShardedGCN` are out of scope.  `dropout` is one rate for
+    all members (a float) or K rates in [0, 1), one per member.
 
     `layers[0]` is ONE `GCNConv(in_channels, K h)` -- member k owns columns [k h, (k + 1) h) -- so activation reuse, the
     optimizer fused into the backward SpMM and every feature format apply as they do to `GCN`.  `layers[1]` is a
@@ -194,7 +349,11 @@ class PerLabelGCN(nn.Module):
     at multiples of 4 columns and the pad columns between them carry zero weight and bias, which the loss never reads.
 
     Dropout follows the package's rule: torch's `F.dropout` on H1cat from torch's stream by default; after
-    `enable_fused_dropout()` and with 0 < p < 1 each member's product is `dense.xw_dropout` under its own seed.
+    `enable_fused_dropout()` and with 0 < p < 1 each member's product is `dense.xw_dropout` under its own seed.  With a rate
+    per member the fused form hands the K rates to `block_diag_xw` (a fresh seed per member, a member at rate 0 keeps
+    everything); on torch's stream the dropout is `F.dropout` per column block with its rate, which costs K small launches
+    and a concatenation per step.  `enable_fused_block_diag()` runs the three layer-2 products as one launch each for all
+    K members.  Eval mode drops nothing in any form.
 
     `from_members` / `export_members` copy parameters from / to K ordinary `GCN` modules -- the objects
     perlabel_amazon.py:154 saves with `th.save(gcn, "lvl2-cat{k}")` and eval_perlabel.py:16-19 loads; a checkpoint of the
@@ -206,8 +365,10 @@ class PerLabelGCN(nn.Module):
         self.class_counts = tuple(int(c) for c in class_counts)
         if not self.class_counts:
             raise ValueError("PerLabelGCN needs at least one group")
-        self.in_channels, self.n_hidden, self.dropout = int(in_channels), int(n_hidden_gcn), dropout
-        K, h = len(self.class_counts), self.n_hidden
+        K = len(self.class_counts)
+        self.in_channels, self.n_hidden = int(in_channels), int(n_hidden_gcn)
+        self.dropout = member_rates(dropout, K, type(self).__name__)       # a float, or a tuple of K rates
+        h = self.n_hidden
         first = GCNConv(self.in_channels, K * h, add_self_loops=True)
         with torch.no_grad():                  # glorot of a GCNConv(in, h): the same bound for every member
             a = math.sqrt(6.0 / (self.in_channels + h))
@@ -235,10 +396,11 @@ class PerLabelGCN(nn.Module):
         the rows that will be read; the last propagate step runs on the operator restricted to them, as in `GCN`."""
         first, second = self.layers
         x = first(g.x, g.edge_index, g.edge_attr)
-        p = float(self.dropout) if self.training else 0.0
-        if models._FUSED_DROPOUT and 0.0 < p < 1.0:
+        if isinstance(self.dropout, tuple):
+            xw = self._xw_member_rates(x, second.weight)
+        elif models._FUSED_DROPOUT and self.training and 0.0 < float(self.dropout) < 1.0:
             seeds = torch.empty(self.n_groups, dtype=torch.int64, device=x.device).random_()
-            xw = block_diag_xw(x, second.weight, self.seg_start, self.seg_width, p, seeds)
+            xw = block_diag_xw(x, second.weight, self.seg_start, self.seg_width, float(self.dropout), seeds)
         else:
             x = nn.functional.dropout(x, p=self.dropout, training=self.training)
             xw = block_diag_xw(x, second.weight, self.seg_start, self.seg_width)
@@ -246,6 +408,31 @@ class PerLabelGCN(nn.Module):
         if rows is not None:
             plan = plan.on_rows(rows) or plan
         return propagate(plan, xw, second.bias)
+
+    def _xw_member_rates(self, x: Tensor, weight: Tensor) -> Tensor:
+        """dropout(H1cat) blockdiag(W2) with a rate per member (`self.dropout` is a tuple)."""
+        rates, h = self.dropout, self.n_hidden
+        if not self.training or max(rates) == 0.0:
+            return block_diag_xw(x, weight, self.seg_start, self.seg_width)
+        if models._FUSED_DROPOUT:
+            seeds = torch.empty(self.n_groups, dtype=torch.int64, device=x.device).random_()
+            return block_diag_xw(x, weight, self.seg_start, self.seg_width, rates, seeds)
+        # torch's stream: F.dropout per column block with its rate (K small launches and one concatenation)
+        x = torch.cat([nn.functional.dropout(x[:, k * h:(k + 1) * h], p=p, training=True) for k, p in enumerate(rates)], 1)
+        return block_diag_xw(x, weight, self.seg_start, self.seg_width)
+
+    def member_dropout(self, k: int) -> float:
+        """The dropout rate of member k."""
+        return self.dropout[k] if isinstance(self.dropout, tuple) else self.dropout
+
+    @staticmethod
+    def _rates_of(members, dropout):
+        """`from_members`' rule: `dropout` when it is given; else the members' rates -- a float when they are all equal,
+        the K rates when they differ."""
+        if dropout is not None:
+            return dropout
+        rates = [m.dropout for m in members]
+        return rates[0] if all(r == rates[0] for r in rates) else rates
 
     def loss(self, g, target, mask, group, counts=None, return_pred=False, route=None, class_map=None, rows=None):
         """`grouped_masked_cross_entropy` of `self(g, rows)`: `(loss, loss_k[, pred])`."""
@@ -264,9 +451,11 @@ class PerLabelGCN(nn.Module):
             counts=[0] * self.n_groups, return_pred=True, route=route, class_map=class_map)[2]
 
     @classmethod
-    def from_members(cls, members: Sequence[nn.Module], dropout: Optional[float] = None) -> "PerLabelGCN":
+    def from_members(cls, members: Sequence[nn.Module], dropout=None) -> "PerLabelGCN":
         """One network from K two-layer `GCN`s (or modules with the same `layers.{0,1}.{weight,bias}`, such as the
-        reference's checkpoints loaded into `GCN`) of equal input and hidden width.  Parameters are copied."""
+        reference's checkpoints loaded into `GCN`) of equal input and hidden width.  Parameters are copied.  `dropout`
+        (a float or K floats) overrides the members' rates; without it the network keeps one float when the members'
+        rates are all equal and the K rates when they differ."""
         members = list(members)
         if not members:
             raise ValueError("from_members: no member")
@@ -278,7 +467,7 @@ class PerLabelGCN(nn.Module):
             raise ValueError("from_members: members must carry biases")
         h = w1[0].size(1)
         net = cls(w1[0].size(0), [m.layers[1].weight.size(1) for m in members], n_hidden_gcn=h,
-                  dropout=members[0].dropout if dropout is None else dropout)
+                  dropout=cls._rates_of(members, dropout))
         net = net.to(w1[0].device)
         first, second = net.layers
         with torch.no_grad():
@@ -293,12 +482,12 @@ class PerLabelGCN(nn.Module):
 
     @torch.no_grad()
     def export_members(self) -> List[nn.Module]:
-        """K `GCN(in_channels, C_k, n_hidden_gcn=h, dropout=...)` holding COPIES of the members' parameters, in this
-        network's training mode: what perlabel_amazon.py:154 saves one by one."""
+        """K `GCN(in_channels, C_k, n_hidden_gcn=h, dropout=...)` holding COPIES of the members' parameters, member k with
+        its own rate, in this network's training mode: what perlabel_amazon.py:154 saves one by one."""
         first, second = self.layers
         h, out = self.n_hidden, []
         for k, (s, c) in enumerate(zip(self.seg_start, self.seg_width)):
-            m = models.GCN(self.in_channels, c, n_hidden_gcn=h, dropout=self.dropout).to(first.weight.device)
+            m = models.GCN(self.in_channels, c, n_hidden_gcn=h, dropout=self.member_dropout(k)).to(first.weight.device)
             m.layers[0].weight.copy_(first.weight[:, k * h:(k + 1) * h])
             m.layers[0].bias.copy_(first.bias[k * h:(k + 1) * h])
             m.layers[1].weight.copy_(second.weight[:, s:s + c])
