@@ -352,6 +352,56 @@ int tgcn_member_ce(const float *logits, int64_t ld, int64_t n_rows, int n_member
                    float *dlogits, int64_t ldd, float *dbias, int32_t *pred, void *workspace, size_t workspace_bytes,
                    tgcn_stream stream);
 
+/* Device-side scores of the K-member networks: what the reference takes per member on the host with sklearn's
+ * f1_score(average="macro") and accuracy_score (old/h_o_train.py:116-122).  Both need three numbers per class, not a C x C
+ * confusion matrix: `counts` is int32 [K, 3, C], planes in the order tp, n_pred, n_true.
+ *
+ * tgcn_class_counts_members -- the members of a sweep cell (tgcn_member_ce's selection and prediction):
+ *   pred   int32 [n_rows, K] stride ldp >= K   the member's local arg-max on every row
+ *   target int64 [n_rows]   shared by the members; read only where bits_a | bits_b has a bit below K set
+ *   bits_a uint64 [n_rows]  row r counts for member k of set a where bit k is set (bits at or above K are ignored);
+ *   bits_b the same for set b, or NULL (then counts_b is NULL too).  The two sets -- training and validation rows -- are
+ *          taken in one pass over pred.
+ * tgcn_class_counts_groups -- the per-label form (tgcn_grouped_ce's prediction):
+ *   pred   int64 [n_rows];  pred_offset int32 [K] (device) or NULL (= 0): the row's class is pred[r] - pred_offset[group[r]]
+ *   group  int32 [n_rows] or NULL: the member of row r, -1 = none; NULL = every row belongs to member 0 (the flat network)
+ *   target int64 [n_rows]   the LOCAL class; read only where a mask selects the row and it has a member
+ *   mask_a uint8/bool [n_rows], mask_b the same or NULL (then counts_b is NULL too)
+ *   C is the widest member; the planes of a narrower member are zero beyond its own width.
+ * Both: counts_a / counts_b [K, 3, C] are written whole by the call (nothing to clear).  A selected row whose prediction
+ * lies outside [0, C) counts in n_true and nothing else (a miss: the -1 of a route of -1).  A selected row whose target lies
+ * outside [0, C) is the caller's error (pytextgcn_amd.metrics raises for it before the launch): the kernel compares the
+ * target with the bounds before it uses it and counts such a row nowhere.  A group outside [-1, K) counts nowhere either.
+ * Each workgroup owns tiles of TGCN_CLASS_COUNTS_ROWS_PER_WORKGROUP rows (at most TGCN_CLASS_COUNTS_WORKGROUP_CAP workgroups
+ * walk the tiles), accumulates with LDS integer adds in a table of at most TGCN_CLASS_COUNTS_LDS_BYTES -- members, and for
+ * wide members the two sets, are tiled over the grid when K * 3 * C * 4 bytes (twice that with set b) exceed it -- and
+ * stores its partial table to the workspace (together at most TGCN_CLASS_COUNTS_PARTIAL_BYTES, or one workgroup's); a
+ * second kernel sums the partials in workgroup order.  No global atomics, no handshake between workgroups; only enqueues on
+ * `stream` (legal under HIP-graph capture).  TGCN_E_INVALID before anything is enqueued for K outside 1..64, C outside
+ * 1..TGCN_CLASS_COUNTS_MAX_CLASSES, n_rows outside 0..2^31-1, ldp < K, a NULL pred / target / bits_a / mask_a (n_rows > 0)
+ * or counts_a, or one of set b's two pointers without the other; TGCN_E_WORKSPACE for a workspace below
+ * tgcn_class_counts_workspace_bytes (0 for invalid sizes).
+ *
+ * tgcn_class_scores -- scores double [K, 4] from counts [K, 3, C], per member:
+ *   [0] accuracy = sum tp / sum n_true (NaN for a member without a row)
+ *   [1] f1_macro = the mean of 2 tp / (n_pred + n_true) over the classes with n_pred + n_true > 0 -- the union of the
+ *       labels that occur in either array, sklearn's f1_score(average="macro") -- NaN when there is none
+ *   [2] n_rows = sum n_true    [3] n_labels = classes in that mean */
+#define TGCN_CLASS_COUNTS_ROWS_PER_WORKGROUP 256
+#define TGCN_CLASS_COUNTS_WORKGROUP_CAP 1024
+#define TGCN_CLASS_COUNTS_LDS_BYTES 49152
+#define TGCN_CLASS_COUNTS_PARTIAL_BYTES 67108864
+#define TGCN_CLASS_COUNTS_MAX_CLASSES 4096
+size_t tgcn_class_counts_workspace_bytes(int64_t n_rows, int n_members, int n_classes);
+int tgcn_class_counts_members(const int32_t *pred, int64_t ldp, const int64_t *target, const uint64_t *bits_a,
+                              const uint64_t *bits_b, int64_t n_rows, int n_members, int n_classes, int32_t *counts_a,
+                              int32_t *counts_b, void *workspace, size_t workspace_bytes, tgcn_stream stream);
+int tgcn_class_counts_groups(const int64_t *pred, const int32_t *pred_offset, const int64_t *target, const int32_t *group,
+                             const uint8_t *mask_a, const uint8_t *mask_b, int64_t n_rows, int n_members, int n_classes,
+                             int32_t *counts_a, int32_t *counts_b, void *workspace, size_t workspace_bytes,
+                             tgcn_stream stream);
+int tgcn_class_scores(const int32_t *counts, int n_members, int n_classes, double *scores, tgcn_stream stream);
+
 /* tgcn_adam_step -- one `torch.optim.Adam(..., amsgrad=...)` update of a flat fp32 tensor
  * (flat_amazon.py:89,106), torch's single-tensor formula op for op, fused into one pass.
  * max_exp_avg_sq = NULL means amsgrad=False.  `step` is the 1-based step count AFTER increment. */

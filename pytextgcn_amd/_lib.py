@@ -85,6 +85,12 @@ SIGNATURES = {
     "tgcn_adam_members_capturable": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int,
                                              c_int, c_void_p, c_double, c_double, c_double, c_double, c_void_p, c_void_p,
                                              c_void_p]),
+    "tgcn_class_counts_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "tgcn_class_counts_members": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p,
+                                          c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tgcn_class_counts_groups": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tgcn_class_scores": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "tgcn_gemm_nn": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int,
                              c_void_p]),
     "tgcn_gemm_nt": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int,

@@ -148,6 +148,18 @@ class CrossValGCN(PerLabelGCN):
             self.train(was)
         return loss_k, pred
 
+    @torch.no_grad()
+    def score(self, g, target, train_bits, val_bits, counts=None, rows=None):
+        """`evaluate` with the scores taken on the device: `(val_loss_k [K], train_scores, val_scores)`, two
+        `metrics.Scores(accuracy, f1_macro, n_rows, n_labels)` of float64 [K] device tensors -- every member's scores on the
+        rows its bit of `train_bits` / `val_bits` selects (old/h_o_train.py:116-122 reads the training accuracy and the
+        validation macro-F1).  One eval forward, one `tgcn_member_ce` with predictions, one count launch for both row sets
+        and two score launches; no host round trip (`counts`: the validation rows per member, as in `evaluate`)."""
+        from . import metrics
+        val_loss_k, pred = self.evaluate(g, target, val_bits, counts, rows)
+        c_train, c_val = metrics.member_class_counts(pred, target, train_bits, self.out_channels, also=val_bits)
+        return val_loss_k, metrics.scores(c_train), metrics.scores(c_val)
+
     @classmethod
     def from_members(cls, members: Sequence[nn.Module], dropout=None) -> "CrossValGCN":
         """One network from K two-layer `GCN`s of equal input, hidden and class width.  Parameters are copied.  `dropout`

@@ -450,6 +450,27 @@ class PerLabelGCN(nn.Module):
             z, torch.zeros(n, dtype=torch.int64, device=z.device), nothing, route, self.seg_start, self.seg_width,
             counts=[0] * self.n_groups, return_pred=True, route=route, class_map=class_map)[2]
 
+    @torch.no_grad()
+    def score(self, g, target, group, train_mask, val_mask, counts=None, rows=None):
+        """The eval forward (no dropout, whatever mode the network is in; the mode is put back) scored on the device:
+        `(val_loss_k [K], train_scores, val_scores)` -- the members' validation losses on `val_mask & (group == k)` and two
+        `metrics.Scores(accuracy, f1_macro, n_rows, n_labels)` of float64 [K] device tensors, member k's on the rows of its
+        group that `train_mask` / `val_mask` select (perlabel_amazon.py:139-150 takes them per label on the host).  One
+        forward, one `tgcn_grouped_ce` with predictions, one count launch for both masks, two score launches; no host
+        round trip (`counts`: the validation rows per group, as in `loss`)."""
+        from . import metrics
+        was = self.training
+        self.eval()
+        try:
+            z = self(g, rows)
+            seg = functional.Segments.of(self.seg_start, self.seg_width, z.device)
+            _, val_loss_k, pred = functional.grouped_masked_cross_entropy(z, target, val_mask, group, seg, None, counts, True)
+        finally:
+            self.train(was)
+        c_train, c_val = metrics.grouped_class_counts(pred, target, train_mask, max(self.class_counts), group, self.n_groups,
+                                                      seg.dev_start, also=val_mask)
+        return val_loss_k, metrics.scores(c_train), metrics.scores(c_val)
+
     @classmethod
     def from_members(cls, members: Sequence[nn.Module], dropout=None) -> "PerLabelGCN":
         """One network from K two-layer `GCN`s (or modules with the same `layers.{0,1}.{weight,bias}`, such as the
@@ -713,6 +734,23 @@ class PerLabelMLP(nn.Module):
             mask = rows.routed
         return functional.grouped_masked_cross_entropy(z, target, mask, group, self.seg_start, self.seg_width, None,
                                                        return_pred, None, class_map)
+
+    @torch.no_grad()
+    def score(self, xg, rows: GroupedRows, target, mask=None):
+        """One split scored on the device (MLP_label.py takes accuracy and F1 per label on the host): `(loss_k [K],
+        scores)` of `self(xg, rows)` in the network's current mode -- call `eval()` first for a validation or test split --
+        with `scores` a `metrics.Scores(accuracy, f1_macro, n_rows, n_labels)` of float64 [K] device tensors, member k's on
+        the rows of its group that `mask` selects (bool [N], grouped order; default: every routed row).  `target` as in
+        `loss`.  No host round trip."""
+        from . import metrics
+        z = self(xg, rows)
+        group = rows._on(z, "group_sorted")
+        if mask is None:
+            mask = rows.routed
+        seg = functional.Segments.of(self.seg_start, self.seg_width, z.device)
+        _, loss_k, pred = functional.grouped_masked_cross_entropy(z, target, mask, group, seg, None, None, True)
+        counts = metrics.grouped_class_counts(pred, target, mask, max(self.class_counts), group, self.n_groups, seg.dev_start)
+        return loss_k, metrics.scores(counts)
 
     @torch.no_grad()
     def predict(self, xg, rows: GroupedRows, class_map=None) -> Tensor:

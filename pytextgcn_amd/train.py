@@ -136,6 +136,7 @@ class FlatLoop:
         dtype = torch.uint8 if n_classes <= 256 else torch.int16 if n_classes <= 32767 else torch.int32
         self._pred_host = torch.empty(self._rows.numel(), dtype=dtype).pin_memory()
         self._loss_host = torch.empty(2, dtype=torch.float32).pin_memory()
+        self._n_classes, self._scored_host = n_classes, None
         self.epochs = 0
 
     def _fwd(self, rows):
@@ -160,6 +161,32 @@ class FlatLoop:
         self.epochs += 1
         p = self._pred_host.numpy()
         return float(self._loss_host[0]), float(self._loss_host[1]), p[:self._n_val], p[self._n_val:]
+
+    def epoch_scored(self):
+        """`epoch()` with the two scores of flat_amazon.py:111-114 taken on the device (`metrics.grouped_class_counts`
+        without groups, `metrics.scores`): returns `(training loss, validation loss, training accuracy, validation
+        macro-F1)` as floats.  The same training step, evaluation pass and one synchronisation per epoch; four scalars
+        cross to the host instead of the predictions."""
+        from . import metrics
+        model, g, opt = self.model, self.g, self.optimizer
+        if self._scored_host is None:
+            self._scored_host = torch.empty(4, dtype=torch.float64).pin_memory()
+            self._y64 = g.y.long()                   # (g.y itself when it is int64: the labels are static)
+        model.train()
+        loss = masked_cross_entropy(self._fwd(self.rows_train), g.y, g.train_mask)
+        opt.zero_grad(set_to_none=True)
+        loss.backward()
+        opt.step()
+        model.eval()
+        with torch.no_grad():
+            val_loss, pred = masked_cross_entropy(self._fwd(self.rows_eval), g.y, g.val_mask, return_pred=True)
+            c_train, c_val = metrics.grouped_class_counts(pred, self._y64, g.train_mask, self._n_classes, also=g.val_mask)
+            four = torch.stack([loss.detach().double(), val_loss.double(), metrics.scores(c_train).accuracy[0],
+                                metrics.scores(c_val).f1_macro[0]])
+            self._scored_host.copy_(four, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        self.epochs += 1
+        return tuple(float(v) for v in self._scored_host)
 
     def test(self):
         """Predicted classes of the test rows (flat_amazon.py:130-131), as numpy."""
