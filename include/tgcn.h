@@ -425,6 +425,21 @@ int tgcn_adam_members_capturable(float *param, const float *grad, float *exp_avg
                                  double beta1, double beta2, double eps, double weight_decay, int64_t *step_dev,
                                  float *scalars_dev, tgcn_stream stream);
 
+/* tgcn_adam_member_rows -- tgcn_adam_step on a flat tensor of n = n_members * block elements whose members are ROW blocks
+ * (the stacked [M D, in] embedding weight of a CrossValEGCN): element i takes lr_host[i / block].  n and block are 64-bit
+ * and so is every index: such a tensor passes 2^31 elements.  16-byte bodies where block is a multiple of 4, 4-byte
+ * accesses otherwise.  Block k after the call is bit for bit what tgcn_adam_step with lr_host[k] gives on that contiguous
+ * range.  The capturable form is tgcn_adam_members_capturable's (K + 1 scalars on the device).  n == 0 is a no-op (the
+ * capturable form still advances the step).  TGCN_E_INVALID before anything is enqueued for n != K * block, K outside
+ * 1..64, a NULL lr_host, a negative size or buffers that are not 16-byte aligned.  Additive to ABI 7. */
+int tgcn_adam_member_rows(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, float *max_exp_avg_sq,
+                          int64_t n, int64_t block, int n_members, const double *lr_host, double beta1, double beta2,
+                          double eps, double weight_decay, int64_t step, tgcn_stream stream);
+int tgcn_adam_member_rows_capturable(float *param, const float *grad, float *exp_avg, float *exp_avg_sq,
+                                     float *max_exp_avg_sq, int64_t n, int64_t block, int n_members, const double *lr_host,
+                                     double beta1, double beta2, double eps, double weight_decay, int64_t *step_dev,
+                                     float *scalars_dev, tgcn_stream stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Tall-skinny fp32 GEMMs on the matrix cores (v_mfma_f32_32x32x2_f32, exact fp32): the dense
  * `torch.matmul(x, self.weight)` of PyG-1.6.3 GCNConv.forward (reference call site models.py:20,
@@ -569,6 +584,31 @@ int tgcn_embed_xw_h_grad(const float *E, int64_t lde, const float *b, const floa
                          float *dE, int64_t ldde, float *db, float *dEh, int64_t lddeh, float *dW, int64_t lddw, int64_t N,
                          int K, int n, double p, const uint64_t *seed, int64_t mask_row0, void *workspace,
                          size_t workspace_bytes, tgcn_stream stream);
+
+/* The same front end for M = n_members (1..64) networks of equal widths in one call: the EGCN members of a sweep cell
+ * (pytextgcn_amd/crossval.py: CrossValEGCN).  Additive to ABI 7.  E, b, Eh and W are stacked by ROWS -- member m owns the
+ * rows [m K, (m + 1) K) of E [M K, N], b [M K], Eh [M K, Fh] and W [M K, n] -- and so are dE, db, dEh and dW; C and G are
+ * [N, M n] (ldc, ldg >= M n) and member m owns their columns [m n, (m + 1) n).  Hd, h_row0 and Fh are the members' common
+ * ones; Fh == 0 (Eh and Hd are then not looked at) means identity features.  p_host: M rates on the HOST, each in
+ * [0, 1); seeds: M seeds on the DEVICE, NULL for the eval product.  keep_m(i, k) is the decision of tgcn_gemm_*_dropout
+ * for seeds[m], mask row mask_row0 + i and column k < K inside the member, at p_host[m]; a member at rate 0 keeps
+ * everything at scale 1.  Member m's blocks of every result are BIT FOR BIT what tgcn_embed_xw[_h][_grad] gives with
+ * seeds + m, p_host[m] and the member's slices: the same kernels run with the member as one more grid dimension, so the
+ * number of launches does not depend on M.  The nodes are cut into slices as the single call cuts them for (N, K); the
+ * workspace is M times the single call's.  No atomics, fixed summation orders; the calls only enqueue on `stream` (N == 0:
+ * memsets of the sums).  TGCN_E_INVALID before anything is enqueued for M outside 1..64, a rate outside [0, 1), a leading
+ * dimension below the width, NULL operands with N > 0, dE without db (or, with Fh > 0, dEh), Fh outside [0, 128] and
+ * h_row0 outside [0, N]; TGCN_E_WORKSPACE for a short workspace. */
+int tgcn_embed_xw_members(const float *E, int64_t lde, const float *b, const float *Eh, int64_t ldeh, const float *Hd,
+                          int64_t ldh, int64_t h_row0, int Fh, const float *W, int64_t ldw, float *C, int64_t ldc, int64_t N,
+                          int K, int n, int n_members, const double *p_host, const uint64_t *seeds, int64_t mask_row0,
+                          tgcn_stream stream);
+size_t tgcn_embed_xw_members_grad_workspace_bytes(int64_t N, int K, int n, int Fh, int n_members);
+int tgcn_embed_xw_members_grad(const float *E, int64_t lde, const float *b, const float *Eh, int64_t ldeh, const float *Hd,
+                               int64_t ldh, int64_t h_row0, int Fh, const float *W, int64_t ldw, const float *G, int64_t ldg,
+                               float *dE, int64_t ldde, float *db, float *dEh, int64_t lddeh, float *dW, int64_t lddw,
+                               int64_t N, int K, int n, int n_members, const double *p_host, const uint64_t *seeds,
+                               int64_t mask_row0, void *workspace, size_t workspace_bytes, tgcn_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The first GCNConv's x @ W on [I_N | H] features for the plain GCN of the per-level scripts (perlevel_amazon.py:122,156;

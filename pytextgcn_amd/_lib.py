@@ -85,6 +85,11 @@ SIGNATURES = {
     "tgcn_adam_members_capturable": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int,
                                              c_int, c_void_p, c_double, c_double, c_double, c_double, c_void_p, c_void_p,
                                              c_void_p]),
+    "tgcn_adam_member_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p,
+                                      c_double, c_double, c_double, c_double, c_int64, c_void_p]),
+    "tgcn_adam_member_rows_capturable": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int,
+                                                 c_void_p, c_double, c_double, c_double, c_double, c_void_p, c_void_p,
+                                                 c_void_p]),
     "tgcn_class_counts_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "tgcn_class_counts_members": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p,
                                           c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -130,6 +135,14 @@ SIGNATURES = {
                                      c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
                                      c_void_p, c_int64, c_int64, c_int, c_int, c_double, c_void_p, c_int64, c_void_p,
                                      c_size_t, c_void_p]),
+    "tgcn_embed_xw_members": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int,
+                                      c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_void_p,
+                                      c_int64, c_void_p]),
+    "tgcn_embed_xw_members_grad_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int, c_int]),
+    "tgcn_embed_xw_members_grad": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int,
+                                           c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                           c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_void_p,
+                                           c_int64, c_void_p, c_size_t, c_void_p]),
     "tgcn_hier_max_features": (c_int, []),
     "tgcn_hier_xw": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_int64,
                              c_int, c_void_p]),

@@ -13,7 +13,9 @@
 //   k_adam_members   tgcn_adam_step on a [n_rows, K * member_width] tensor whose column block k takes the rate lr[k]: the
 //                    members are column blocks of shared tensors and Adam is elementwise, so block k after a step is bit for
 //                    bit what tgcn_adam_step with lr[k] gives on a contiguous copy of it (the same adam_element).
-// Both are deterministic (fixed-order two-stage reductions, no atomics) and only enqueue on the caller's stream.
+//   k_adam_member_rows  the same with the members as contiguous ROW blocks of a flat tensor (the stacked tensors of a
+//                    CrossValEGCN), every index 64-bit: such a tensor passes 2^31 elements.
+// All are deterministic (fixed-order two-stage reductions, no atomics) and only enqueue on the caller's stream.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -407,6 +409,60 @@ __global__ __launch_bounds__(256) void k_adam_members(float *__restrict__ p, con
     }
 }
 
+// The members as ROW blocks (the stacked embedding weight [M D, in] of a CrossValEGCN): a flat tensor of n = K * block
+// elements, element i takes the rate of member i / block.  Such a tensor passes 2^31 elements (12 members at 100 000
+// nodes and D = 2000 are 2.4e9), so every index here is 64-bit.  V4 (block a multiple of 4, hence n too): the four
+// elements of a 16-byte body lie in one member and there is no tail.  Otherwise every element looks its member up.
+template <bool AMSGRAD, bool NT, bool V4>
+__global__ __launch_bounds__(256) void k_adam_member_rows(float *__restrict__ p, const float *__restrict__ g,
+                                                          float *__restrict__ m, float *__restrict__ v,
+                                                          float *__restrict__ vmax, int64_t n, int64_t block, int K,
+                                                          float w1 /* 1-b1 */, float b2, float w2 /* 1-b2 */, float eps,
+                                                          float wd, const MemberRates host, float inv_bc2_sqrt,
+                                                          const float *__restrict__ dev_scalars) {
+    __shared__ float rate[kMaxMembers];
+    if (static_cast<int>(threadIdx.x) < K)
+        rate[threadIdx.x] = dev_scalars != nullptr ? dev_scalars[threadIdx.x] : host.step_size[threadIdx.x];
+    if (dev_scalars != nullptr) inv_bc2_sqrt = dev_scalars[K];
+    __syncthreads();
+    const int64_t stride = int64_t(gridDim.x) * blockDim.x * 4;
+    for (int64_t i = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
+        if constexpr (V4) {
+            const float step_size = rate[i / block];
+            float4 pp = *reinterpret_cast<float4 *>(p + i);
+            const float4 gg = ld4<NT>(g + i);
+            float4 mm = ld4<NT>(m + i);
+            float4 vv = ld4<NT>(v + i);
+            float4 xx = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (AMSGRAD) xx = ld4<NT>(vmax + i);
+            float *P = &pp.x, *M = &mm.x, *V = &vv.x, *X = &xx.x;
+            const float *G = &gg.x;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                adam_element(P[k], G[k], M[k], V[k], X[k], AMSGRAD, w1, b2, w2, eps, wd, step_size, inv_bc2_sqrt);
+            *reinterpret_cast<float4 *>(p + i) = pp;
+            st4<NT>(m + i, mm);
+            st4<NT>(v + i, vv);
+            if (AMSGRAD) st4<NT>(vmax + i, xx);
+        } else {
+            int64_t k = i / block, left = (k + 1) * block - i;     // elements of member k from i on
+            const int64_t end = i + 4 < n ? i + 4 : n;
+            for (int64_t j = i; j < end; ++j) {
+                float pj = p[j], mj = m[j], vj = v[j], xj = AMSGRAD ? vmax[j] : 0.f;
+                adam_element(pj, g[j], mj, vj, xj, AMSGRAD, w1, b2, w2, eps, wd, rate[k], inv_bc2_sqrt);
+                p[j] = pj;
+                m[j] = mj;
+                v[j] = vj;
+                if (AMSGRAD) vmax[j] = xj;
+                if (--left == 0) {
+                    ++k;
+                    left = block;
+                }
+            }
+        }
+    }
+}
+
 }  // namespace
 }  // namespace tgcn
 
@@ -601,6 +657,90 @@ int tgcn_adam_members_capturable(float *param, const float *grad, float *exp_avg
     return adam_members_impl("tgcn_adam_members_capturable", param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, n_rows,
                              n_cols, member_width, n_members, lr_host, beta1, beta2, eps, weight_decay, 1, step_dev,
                              scalars_dev, stream);
+}
+
+static int adam_member_rows_impl(const char *who, float *param, const float *grad, float *exp_avg, float *exp_avg_sq,
+                                 float *max_exp_avg_sq, int64_t n, int64_t block, int n_members, const double *lr_host,
+                                 double beta1, double beta2, double eps, double weight_decay, int64_t step, int64_t *step_dev,
+                                 float *scalars_dev, tgcn_stream stream) {
+    using namespace tgcn;
+    const int K = n_members;
+    if (K < 1 || K > kMaxMembers || !lr_host || n < 0 || block < 0 || block > INT64_MAX / K || n != int64_t(K) * block ||
+        step < 1) {
+        set_error("%s: bad argument (n=%lld must be n_members=%d (1..%d) * block=%lld; lr_host=%s step=%lld)", who,
+                  (long long)n, K, kMaxMembers, (long long)block, lr_host ? "given" : "NULL", (long long)step);
+        return TGCN_E_INVALID;
+    }
+    if (n > 0 && (!param || !grad || !exp_avg || !exp_avg_sq)) {
+        set_error("%s: NULL param / grad / exp_avg / exp_avg_sq", who);
+        return TGCN_E_INVALID;
+    }
+    const uintptr_t al = reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) |
+                         reinterpret_cast<uintptr_t>(exp_avg) | reinterpret_cast<uintptr_t>(exp_avg_sq) |
+                         reinterpret_cast<uintptr_t>(max_exp_avg_sq);
+    if (n > 0 && al % 16 != 0) {
+        set_error("%s: buffers must be 16-byte aligned", who);
+        return TGCN_E_INVALID;
+    }
+    if (n == 0 && step_dev == nullptr) return TGCN_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // every constant in double, rounded once (adam_impl of train.hip)
+    const double bc1 = 1.0 - std::pow(beta1, static_cast<double>(step));
+    const double bc2 = 1.0 - std::pow(beta2, static_cast<double>(step));
+    MemberRates rates{};
+    for (int k = 0; k < K; ++k) rates.step_size[k] = static_cast<float>(lr_host[k] / bc1);
+    const float w1 = static_cast<float>(1.0 - beta1), w2 = static_cast<float>(1.0 - beta2);
+    const float b2f = static_cast<float>(beta2), epsf = static_cast<float>(eps), wdf = static_cast<float>(weight_decay);
+    const float inv_bc2_sqrt = static_cast<float>(1.0 / std::sqrt(bc2));
+    if (step_dev != nullptr) {
+        MemberLrs lrs{};
+        for (int k = 0; k < K; ++k) lrs.lr[k] = lr_host[k];
+        k_adam_member_scalars<<<1, 64, 0, s>>>(step_dev, lrs, K, beta1, beta2, scalars_dev);
+        TGCN_HIP_CHECK(hipGetLastError());
+        if (n == 0) return TGCN_OK;
+    }
+    const int grid = static_cast<int>(std::min<int64_t>(8192, (n / 4 + 255) / 256 + 1));
+    const bool nt = n >= (int64_t(1) << 24);
+    const bool v4 = block % 4 == 0;
+#define TGCN_RADAM3(AMS, NTV, V4V)                                                                                        \
+    k_adam_member_rows<AMS, NTV, V4V><<<grid, 256, 0, s>>>(param, grad, exp_avg, exp_avg_sq,                              \
+                                                           AMS ? max_exp_avg_sq : nullptr, n, block, K, w1, b2f, w2, epsf, \
+                                                           wdf, rates, inv_bc2_sqrt, scalars_dev)
+#define TGCN_RADAM2(AMS, NTV)                                       \
+    do {                                                            \
+        if (v4)                                                     \
+            TGCN_RADAM3(AMS, NTV, true);                            \
+        else                                                        \
+            TGCN_RADAM3(AMS, NTV, false);                           \
+    } while (0)
+    if (max_exp_avg_sq) {
+        if (nt) TGCN_RADAM2(true, true); else TGCN_RADAM2(true, false);
+    } else {
+        if (nt) TGCN_RADAM2(false, true); else TGCN_RADAM2(false, false);
+    }
+#undef TGCN_RADAM2
+#undef TGCN_RADAM3
+    TGCN_HIP_CHECK(hipGetLastError());
+    return TGCN_OK;
+}
+
+int tgcn_adam_member_rows(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, float *max_exp_avg_sq,
+                          int64_t n, int64_t block, int n_members, const double *lr_host, double beta1, double beta2,
+                          double eps, double weight_decay, int64_t step, tgcn_stream stream) {
+    return adam_member_rows_impl("tgcn_adam_member_rows", param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, n, block,
+                                 n_members, lr_host, beta1, beta2, eps, weight_decay, step, nullptr, nullptr, stream);
+}
+
+int tgcn_adam_member_rows_capturable(float *param, const float *grad, float *exp_avg, float *exp_avg_sq,
+                                     float *max_exp_avg_sq, int64_t n, int64_t block, int n_members, const double *lr_host,
+                                     double beta1, double beta2, double eps, double weight_decay, int64_t *step_dev,
+                                     float *scalars_dev, tgcn_stream stream) {
+    if (!step_dev || !scalars_dev) {
+        tgcn::set_error("tgcn_adam_member_rows_capturable: step_dev / scalars_dev must be device pointers");
+        return TGCN_E_INVALID;
+    }
+    return adam_member_rows_impl("tgcn_adam_member_rows_capturable", param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, n,
+                                 block, n_members, lr_host, beta1, beta2, eps, weight_decay, 1, step_dev, scalars_dev, stream);
 }
 
 }  // extern "C"

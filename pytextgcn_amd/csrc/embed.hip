@@ -14,6 +14,9 @@
 //     z(i, k) = (E[k, i] + b[k]) + t(i, k),      t(i, k) = sum_f H[i, f] Eh[k, f]   (f ascending, one fma each),
 // and dEh joins the gradients.  They are the HIER = true instantiations of the same kernels.
 //
+// tgcn_embed_xw_members / tgcn_embed_xw_members_grad run the same kernel bodies for M networks of equal widths whose
+// parameters are stacked by rows (the EGCN members of a sweep cell): the member is one more grid dimension.
+//
 // All products run on v_mfma_f32_32x32x2_f32 (fragment maps: fused_act.h).  E's layout suits them: for a fixed k the 32
 // nodes of a tile are contiguous, so a wave's operand load is two 128-byte runs and no transpose is needed; the loads are
 // scalar dwords because a contiguous [K, N] parameter has 16-byte rows only when N % 4 == 0.
@@ -105,9 +108,9 @@ __device__ __forceinline__ f32x16 h_term(const float *Ehs, const float (&hreg)[k
 // element a(i, k) -- its node i is fixed, so the row key of the hash is paid once per lane -- and spends it on NT tiles.
 // ---------------------------------------------------------------------------------------------
 template <int NT, bool DROP, bool HIER>
-__global__ __launch_bounds__(256, 2) void k_embed_fwd(const float *__restrict__ E, int64_t lde, const float *__restrict__ b,
-                                                      const float *__restrict__ W, int64_t ldw, float *__restrict__ C,
-                                                      int64_t ldc, int64_t N, int K, int n, const EmbedTail<HIER> a) {
+__device__ __forceinline__ void embed_fwd(const float *__restrict__ E, int64_t lde, const float *__restrict__ b,
+                                          const float *__restrict__ W, int64_t ldw, float *__restrict__ C, int64_t ldc,
+                                          int64_t N, int K, int n, const EmbedTail<HIER> &a) {
     constexpr int KC = 32, NP = 32 * NT;
     __shared__ float Ws[KC * NP];
     __shared__ float Ehs[HIER ? KC * kHLd : 1];            // (HIER = false: never referenced, not allocated)
@@ -180,6 +183,51 @@ __global__ __launch_bounds__(256, 2) void k_embed_fwd(const float *__restrict__ 
     }
 }
 
+template <int NT, bool DROP, bool HIER>
+__global__ __launch_bounds__(256, 2) void k_embed_fwd(const float *__restrict__ E, int64_t lde, const float *__restrict__ b,
+                                                      const float *__restrict__ W, int64_t ldw, float *__restrict__ C,
+                                                      int64_t ldc, int64_t N, int K, int n, const EmbedTail<HIER> a) {
+    embed_fwd<NT, DROP, HIER>(E, lde, b, W, ldw, C, ldc, N, K, n, a);
+}
+
+// ---------------------------------------------------------------------------------------------
+// M members in one launch (tgcn_embed_xw_members*): E, b, Eh, W and their gradients are stacked by rows -- member m owns
+// the rows [m K, (m + 1) K) -- and C / G by columns, member m owning [m nm, (m + 1) nm).  The member is one more grid
+// dimension: it moves the operands to the member's blocks, selects the member's seed, threshold and scale, and runs the
+// kernel body above on them -- the same arithmetic in the same order as the single call with that member's slices, so
+// the same bits.  A member at rate 0 has threshold 0 and scale 1: every element is kept and x * 1.f is x.
+// ---------------------------------------------------------------------------------------------
+constexpr int kMaxMembers = 64;
+
+struct MemberDrop {
+    uint32_t thresh[kMaxMembers];
+    float scale[kMaxMembers];
+};
+
+template <bool DROP, bool HIER>
+__device__ __forceinline__ EmbedTail<HIER> member_tail(const EmbedTail<HIER> &a, const MemberDrop &md, int m, int K) {
+    EmbedTail<HIER> t = a;
+    if constexpr (HIER) t.h.Eh += int64_t(m) * K * t.h.ldeh;
+    if constexpr (DROP) {
+        t.d.seed += m;
+        t.d.thresh = md.thresh[m];
+        t.d.scale = md.scale[m];
+    }
+    return t;
+}
+
+template <int NT, bool DROP, bool HIER>
+__global__ __launch_bounds__(256, 2) void k_embed_fwd_members(const float *__restrict__ E, int64_t lde,
+                                                              const float *__restrict__ b, const float *__restrict__ W,
+                                                              int64_t ldw, float *__restrict__ C, int64_t ldc, int64_t N,
+                                                              int K, int n, int nm, const EmbedTail<HIER> a,
+                                                              const MemberDrop md) {
+    const int m = blockIdx.y;
+    const int64_t r0 = int64_t(m) * K;
+    embed_fwd<NT, DROP, HIER>(E + r0 * lde, lde, b + r0, W + r0 * ldw, ldw, C + int64_t(m) * nm, ldc, N, K, n,
+                              member_tail<DROP, HIER>(a, md, m, K));
+}
+
 // ---------------------------------------------------------------------------------------------
 // dE, in E's layout.  The tile is computed transposed, T[k, i] = sum_j W[k, j] G[i, j], so that the 32 nodes of a tile are
 // the lanes of a store (two 128-byte runs per register).  A wave keeps its 32 rows of G in registers (the B operand; loaded
@@ -190,11 +238,10 @@ __global__ __launch_bounds__(256, 2) void k_embed_fwd(const float *__restrict__ 
 // k_embed_h_grad_eh.)
 // ---------------------------------------------------------------------------------------------
 template <int NT, bool DROP, bool HIER>
-__global__ __launch_bounds__(256, 2) void k_embed_grad_e(const float *__restrict__ E, int64_t lde, const float *__restrict__ b,
-                                                         const float *__restrict__ W, int64_t ldw,
-                                                         const float *__restrict__ G, int64_t ldg, float *__restrict__ dE,
-                                                         int64_t ldde, int64_t N, int K, int n, int accum,
-                                                         const EmbedTail<HIER> a) {
+__device__ __forceinline__ void embed_grad_e(const float *__restrict__ E, int64_t lde, const float *__restrict__ b,
+                                             const float *__restrict__ W, int64_t ldw, const float *__restrict__ G,
+                                             int64_t ldg, float *__restrict__ dE, int64_t ldde, int64_t N, int K, int n,
+                                             int accum, const EmbedTail<HIER> &a) {
     constexpr int NP = 32 * NT, LDW = 33;
     __shared__ float Ws[NP * LDW];
     __shared__ float Ehs[HIER ? 32 * kHLd : 1];
@@ -266,6 +313,28 @@ __global__ __launch_bounds__(256, 2) void k_embed_grad_e(const float *__restrict
     }
 }
 
+template <int NT, bool DROP, bool HIER>
+__global__ __launch_bounds__(256, 2) void k_embed_grad_e(const float *__restrict__ E, int64_t lde, const float *__restrict__ b,
+                                                         const float *__restrict__ W, int64_t ldw,
+                                                         const float *__restrict__ G, int64_t ldg, float *__restrict__ dE,
+                                                         int64_t ldde, int64_t N, int K, int n, int accum,
+                                                         const EmbedTail<HIER> a) {
+    embed_grad_e<NT, DROP, HIER>(E, lde, b, W, ldw, G, ldg, dE, ldde, N, K, n, accum, a);
+}
+
+template <int NT, bool DROP, bool HIER>
+__global__ __launch_bounds__(256, 2) void k_embed_grad_e_members(const float *__restrict__ E, int64_t lde,
+                                                                 const float *__restrict__ b, const float *__restrict__ W,
+                                                                 int64_t ldw, const float *__restrict__ G, int64_t ldg,
+                                                                 float *__restrict__ dE, int64_t ldde, int64_t N, int K,
+                                                                 int n, int nm, int accum, const EmbedTail<HIER> a,
+                                                                 const MemberDrop md) {
+    const int m = blockIdx.y;
+    const int64_t r0 = int64_t(m) * K;
+    embed_grad_e<NT, DROP, HIER>(E + r0 * lde, lde, b + r0, W + r0 * ldw, ldw, G + int64_t(m) * nm, ldg, dE + r0 * ldde, ldde,
+                                 N, K, n, accum, member_tail<DROP, HIER>(a, md, m, K));
+}
+
 // db[k] = sum_i dE[k, i]: one workgroup per row of dE, a fixed summation order (no atomics: reproducible run to run)
 __global__ __launch_bounds__(256) void k_embed_rowsum(const float *__restrict__ dE, int64_t ldde, int64_t N,
                                                       float *__restrict__ db) {
@@ -303,10 +372,9 @@ __global__ __launch_bounds__(256) void k_embed_rowsum(const float *__restrict__ 
 // and are added in a fixed order by k_reduce_slices.
 // ---------------------------------------------------------------------------------------------
 template <int TW, bool DROP, bool HIER>
-__global__ __launch_bounds__(256, 2) void k_embed_grad_w(const float *__restrict__ E, int64_t lde, const float *__restrict__ b,
-                                                         const float *__restrict__ G, int64_t ldg, float *__restrict__ part,
-                                                         int64_t N, int K, int n, int64_t chunks_per_slice,
-                                                         const EmbedTail<HIER> a) {
+__device__ __forceinline__ void embed_grad_w(const float *__restrict__ E, int64_t lde, const float *__restrict__ b,
+                                             const float *__restrict__ G, int64_t ldg, float *__restrict__ part, int64_t N,
+                                             int K, int n, int64_t chunks_per_slice, const EmbedTail<HIER> &a) {
     constexpr int LDA = kWChunk + 1, NP = 128 * TW;
     __shared__ float As[32 * LDA];
     __shared__ float Ehs[HIER ? 32 * kHLd : 1];
@@ -411,13 +479,34 @@ __global__ __launch_bounds__(256, 2) void k_embed_grad_w(const float *__restrict
         for (int r = 0; r < 16; ++r) out[int64_t(acc_row(r, half)) * NP + (wave * TW + t) * 32 + c] = acc[t][r];
 }
 
+template <int TW, bool DROP, bool HIER>
+__global__ __launch_bounds__(256, 2) void k_embed_grad_w(const float *__restrict__ E, int64_t lde, const float *__restrict__ b,
+                                                         const float *__restrict__ G, int64_t ldg, float *__restrict__ part,
+                                                         int64_t N, int K, int n, int64_t chunks_per_slice,
+                                                         const EmbedTail<HIER> a) {
+    embed_grad_w<TW, DROP, HIER>(E, lde, b, G, ldg, part, N, K, n, chunks_per_slice, a);
+}
+
+// blockIdx.z is the member; `part_stride`: the floats of one member's partial sums (the single call's workspace)
+template <int TW, bool DROP, bool HIER>
+__global__ __launch_bounds__(256, 2) void k_embed_grad_w_members(const float *__restrict__ E, int64_t lde,
+                                                                 const float *__restrict__ b, const float *__restrict__ G,
+                                                                 int64_t ldg, float *__restrict__ part, int64_t part_stride,
+                                                                 int64_t N, int K, int n, int nm, int64_t chunks_per_slice,
+                                                                 const EmbedTail<HIER> a, const MemberDrop md) {
+    const int m = blockIdx.z;
+    const int64_t r0 = int64_t(m) * K;
+    embed_grad_w<TW, DROP, HIER>(E + r0 * lde, lde, b + r0, G + int64_t(m) * nm, ldg, part + m * part_stride, N, K, n,
+                                 chunks_per_slice, member_tail<DROP, HIER>(a, md, m, K));
+}
+
 // dEh[k, f] = sum_{i >= h0} dE[k, i] H[i, f]: the reduction over the nodes that the kernels above do not have.  The shape
 // of k_embed_grad_w with the finished dE in the place of the activation: blockIdx.x is the tile of k, blockIdx.y one of a
 // FIXED number of slices of the nodes from h0 on; the workgroup stages 32 rows of dE x 128 nodes, the 4 waves take the
 // (at most 4) tiles of 32 features and read their rows of H straight from memory.  The slices' partial sums [32, 128] go
 // to the workspace and k_reduce_slices adds them in slice order: no atomics, the same bits every run.
-__global__ __launch_bounds__(256, 2) void k_embed_h_grad_eh(const float *__restrict__ dE, int64_t ldde, float *__restrict__ part,
-                                                            int64_t N, int K, int64_t chunks_per_slice, const EmbedH h) {
+__device__ __forceinline__ void embed_h_grad_eh(const float *__restrict__ dE, int64_t ldde, float *__restrict__ part,
+                                                int64_t N, int K, int64_t chunks_per_slice, const EmbedH &h) {
     constexpr int LDA = kWChunk + 1, NP = kHMax;
     __shared__ float As[32 * LDA];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, c = lane & 31;
@@ -461,6 +550,27 @@ __global__ __launch_bounds__(256, 2) void k_embed_h_grad_eh(const float *__restr
     float *out = part + (int64_t(blockIdx.y) * kpad + k0) * NP;
 #pragma unroll
     for (int r = 0; r < 16; ++r) out[int64_t(acc_row(r, half)) * NP + f] = acc[r];
+}
+
+__global__ __launch_bounds__(256, 2) void k_embed_h_grad_eh(const float *__restrict__ dE, int64_t ldde, float *__restrict__ part,
+                                                            int64_t N, int K, int64_t chunks_per_slice, const EmbedH h) {
+    embed_h_grad_eh(dE, ldde, part, N, K, chunks_per_slice, h);
+}
+
+// blockIdx.z is the member (Eh is not read here: H and h0 are the members' common ones)
+__global__ __launch_bounds__(256, 2) void k_embed_h_grad_eh_members(const float *__restrict__ dE, int64_t ldde,
+                                                                    float *__restrict__ part, int64_t part_stride, int64_t N,
+                                                                    int K, int64_t chunks_per_slice, const EmbedH h) {
+    const int m = blockIdx.z;
+    embed_h_grad_eh(dE + int64_t(m) * K * ldde, ldde, part + m * part_stride, N, K, chunks_per_slice, h);
+}
+
+// k_reduce_slices for every member: blockIdx.y is the member, whose rows of `out` follow those of the member before
+__global__ __launch_bounds__(256) void k_reduce_slices_members(const float *__restrict__ part, int64_t part_stride, int slices,
+                                                               int64_t slice_stride, int row_stride, int rows, int cols,
+                                                               float *__restrict__ out, int64_t ld) {
+    const int m = blockIdx.y;
+    reduce_slices(part + m * part_stride, slices, slice_stride, row_stride, rows, cols, out + int64_t(m) * rows * ld, ld);
 }
 
 constexpr int kFwdGroup = 256;   // result columns of one forward launch / reduction length of one dE launch (8 tiles)
@@ -676,6 +786,168 @@ int embed_xw_grad(const char *fn, const float *E, int64_t lde, const float *b, c
     return TGCN_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The member-batched calls.  Every launch below is the single call's with the member as one more grid dimension, so
+// the number of launches does not depend on M.
+// ---------------------------------------------------------------------------------------------
+size_t members_part_bytes(int64_t N, int K, int n, int Fh) {   // one member's partial sums: the single call's workspace
+    return Fh > 0 ? std::max(grad_w_bytes(N, K, n), grad_eh_bytes(N, K)) : grad_w_bytes(N, K, n);
+}
+
+struct MembersArgs {
+    const float *E;
+    int64_t lde;
+    const float *b;
+    const float *W;
+    int64_t ldw;
+    int64_t N;
+    int K, n, M;
+    const EmbedH *h;           // nullptr: identity features
+    RowDrop d;                 // seed: the members' seeds [M]; thresh and scale are the member's (MemberDrop)
+    MemberDrop md;
+    hipStream_t s;
+};
+
+template <bool DROP>
+int launch_fwd_members(const MembersArgs &a, float *C, int64_t ldc) {
+    const dim3 grid(static_cast<unsigned>((a.N + 127) / 128), a.M);
+    for (int col0 = 0; col0 < a.n; col0 += kFwdGroup) {
+        const int ng = std::min(a.n - col0, kFwdGroup);
+        with_tiles<1, 2, 4, 7, 8>((ng + 31) / 32, [&](auto nt) {
+            with_hier(a.h, a.d, [&](auto hier, const auto &tail) {
+                hipLaunchKernelGGL((k_embed_fwd_members<decltype(nt)::value, DROP, decltype(hier)::value>), grid, dim3(256), 0,
+                                   a.s, a.E, a.lde, a.b, a.W + col0, a.ldw, C + col0, ldc, a.N, a.K, ng, a.n, tail, a.md);
+            });
+        });
+    }
+    TGCN_HIP_CHECK(hipGetLastError());
+    return TGCN_OK;
+}
+
+template <bool DROP>
+int launch_grad_e_members(const MembersArgs &a, const float *G, int64_t ldg, float *dE, int64_t ldde, float *db, float *dEh,
+                          int64_t lddeh, float *part, int64_t part_stride) {
+    const dim3 grid(static_cast<unsigned>((a.N + 127) / 128), a.M);
+    const int rows = a.M * a.K;
+    for (int col0 = 0; col0 < a.n; col0 += kFwdGroup) {
+        const int ng = std::min(a.n - col0, kFwdGroup), accum = col0 > 0;
+        with_tiles<1, 2, 4, 7, 8>((ng + 31) / 32, [&](auto nt) {
+            with_hier(a.h, a.d, [&](auto hier, const auto &tail) {
+                hipLaunchKernelGGL((k_embed_grad_e_members<decltype(nt)::value, DROP, decltype(hier)::value>), grid,
+                                   dim3(256), 0, a.s, a.E, a.lde, a.b, a.W + col0, a.ldw, G + col0, ldg, dE, ldde, a.N, a.K,
+                                   ng, a.n, accum, tail, a.md);
+            });
+        });
+    }
+    hipLaunchKernelGGL(k_embed_rowsum, dim3(rows), dim3(256), 0, a.s, dE, ldde, a.N, db);   // the members' rows are stacked
+    const EmbedH *h = a.h;
+    if (h && h->h0 == a.N) {
+        TGCN_HIP_CHECK(hipMemset2DAsync(dEh, sizeof(float) * lddeh, 0, sizeof(float) * h->Fh, rows, a.s));
+    } else if (h) {
+        int64_t slices, cps;
+        grad_w_split(a.N, a.K, kWTarget, slices, cps);
+        const int64_t chunks = (a.N - h->h0 + kWChunk - 1) / kWChunk;
+        slices = (chunks + cps - 1) / cps;
+        const int ktiles = (a.K + 31) / 32, kpad = ktiles * 32;
+        hipLaunchKernelGGL(k_embed_h_grad_eh_members, dim3(ktiles, static_cast<unsigned>(slices), a.M), dim3(256), 0, a.s, dE,
+                           ldde, part, part_stride, a.N, a.K, cps, *h);
+        const dim3 rgrid(static_cast<unsigned>((int64_t(a.K) * h->Fh + 255) / 256), a.M);
+        hipLaunchKernelGGL(k_reduce_slices_members, rgrid, dim3(256), 0, a.s, part, part_stride, static_cast<int>(slices),
+                           int64_t(kpad) * kHMax, kHMax, a.K, h->Fh, dEh, lddeh);
+    }
+    TGCN_HIP_CHECK(hipGetLastError());
+    return TGCN_OK;
+}
+
+template <bool DROP>
+int launch_grad_w_members(const MembersArgs &a, const float *G, int64_t ldg, float *dW, int64_t lddw, float *part,
+                          int64_t part_stride) {
+    int64_t slices, cps;
+    grad_w_split(a.N, a.K, kWTarget, slices, cps);
+    const int ktiles = (a.K + 31) / 32, kpad = ktiles * 32;
+    const dim3 grid(ktiles, static_cast<unsigned>(slices), a.M);
+    for (int col0 = 0; col0 < a.n; col0 += kWGroup) {
+        const int ng = std::min(a.n - col0, kWGroup);
+        with_hier(a.h, a.d, [&](auto hier, const auto &tail) {
+            constexpr bool HIER = decltype(hier)::value;
+            if (ng > 128)
+                hipLaunchKernelGGL((k_embed_grad_w_members<2, DROP, HIER>), grid, dim3(256), 0, a.s, a.E, a.lde, a.b, G + col0,
+                                   ldg, part, part_stride, a.N, a.K, ng, a.n, cps, tail, a.md);
+            else
+                hipLaunchKernelGGL((k_embed_grad_w_members<1, DROP, HIER>), grid, dim3(256), 0, a.s, a.E, a.lde, a.b, G + col0,
+                                   ldg, part, part_stride, a.N, a.K, ng, a.n, cps, tail, a.md);
+        });
+        const int np = ng > 128 ? 256 : 128;
+        const dim3 rgrid(static_cast<unsigned>((int64_t(a.K) * ng + 255) / 256), a.M);
+        hipLaunchKernelGGL(k_reduce_slices_members, rgrid, dim3(256), 0, a.s, part, part_stride, static_cast<int>(slices),
+                           int64_t(kpad) * np, np, a.K, ng, dW + col0, lddw);
+    }
+    TGCN_HIP_CHECK(hipGetLastError());
+    return TGCN_OK;
+}
+
+// the checks the two member calls share; fills `a` (but for the stream) and `drop`
+int members_args(const char *fn, const float *E, int64_t lde, const float *b, const EmbedH &h, const float *W, int64_t ldw,
+                 int64_t N, int K, int n, int M, const double *p_host, const uint64_t *seeds, int64_t mask_row0, MembersArgs &a,
+                 bool &drop) {
+    TGCN_CHECK(check_sizes(fn, "K", N, K, n));
+    if (M < 1 || M > kMaxMembers) {
+        set_error("%s: n_members must be in [1, %d] (n_members=%d)", fn, kMaxMembers, M);
+        return TGCN_E_INVALID;
+    }
+    if (int64_t(M) * K > INT32_MAX || int64_t(M) * n > INT32_MAX) {
+        set_error("%s: n_members * K and n_members * n must fit 32 bits", fn);
+        return TGCN_E_INVALID;
+    }
+    if (h.Fh < 0 || h.Fh > kHMax) {
+        set_error("%s: Fh must be in [0, %d] (tgcn_embed_xw_h_max_features; 0: identity features) (Fh=%d)", fn, kHMax, h.Fh);
+        return TGCN_E_INVALID;
+    }
+    if (h.h0 < 0 || h.h0 > N) {
+        set_error("%s: h_row0 must be in [0, N] (h_row0=%lld, N=%lld)", fn, (long long)h.h0, (long long)N);
+        return TGCN_E_INVALID;
+    }
+    TGCN_CHECK(check_ptr(fn, "p_host", p_host));
+    if (mask_row0 < 0) {
+        set_error("%s: mask_row0 must be >= 0 (%lld)", fn, (long long)mask_row0);
+        return TGCN_E_INVALID;
+    }
+    a = MembersArgs{};
+    drop = false;
+    for (int m = 0; m < M; ++m) {
+        const double p = p_host[m];
+        if (!(p >= 0.0 && p < 1.0)) {
+            set_error("%s: every member's p must be in [0, 1) (p[%d]=%g)", fn, m, p);
+            return TGCN_E_INVALID;
+        }
+        const bool on = p > 0.0 && seeds != nullptr;      // (make_row_drop's values, member by member)
+        a.md.thresh[m] = on ? drop_threshold(p) : 0u;
+        a.md.scale[m] = on ? static_cast<float>(1.0 / (1.0 - p)) : 1.f;
+        drop = drop || on;
+    }
+    TGCN_CHECK(check_ld(fn, "lde", lde, N));
+    if (h.Fh > 0) {
+        TGCN_CHECK(check_ld(fn, "ldeh", h.ldeh, h.Fh));
+        TGCN_CHECK(check_ld(fn, "ldh", h.ldh, h.Fh));
+    }
+    TGCN_CHECK(check_ld(fn, "ldw", ldw, n));
+    a.E = E, a.lde = lde, a.b = b, a.W = W, a.ldw = ldw, a.N = N, a.K = K, a.n = n, a.M = M;
+    a.h = h.Fh > 0 ? &h : nullptr;
+    a.d = RowDrop{seeds, 0u, 1.f, mask_row0};
+    return TGCN_OK;
+}
+
+int members_ptrs(const char *fn, const MembersArgs &a) {
+    TGCN_CHECK(check_ptr(fn, "E", a.E));
+    TGCN_CHECK(check_ptr(fn, "b", a.b));
+    if (a.h) {
+        TGCN_CHECK(check_ptr(fn, "Eh", a.h->Eh));
+        if (a.h->h0 < a.N) TGCN_CHECK(check_ptr(fn, "Hd", a.h->Hd));
+    }
+    TGCN_CHECK(check_ptr(fn, "W", a.W));
+    return TGCN_OK;
+}
+
 }  // namespace
 }  // namespace tgcn
 
@@ -721,6 +993,85 @@ int tgcn_embed_xw_h_grad(const float *E, int64_t lde, const float *b, const floa
     const tgcn::EmbedH h{Eh, ldeh, Hd, ldh, h_row0, Fh};
     return tgcn::embed_xw_grad("tgcn_embed_xw_h_grad", E, lde, b, &h, W, ldw, G, ldg, dE, ldde, db, dEh, lddeh, dW, lddw, N, K,
                                n, p, seed, mask_row0, workspace, workspace_bytes, stream);
+}
+
+int tgcn_embed_xw_members(const float *E, int64_t lde, const float *b, const float *Eh, int64_t ldeh, const float *Hd,
+                          int64_t ldh, int64_t h_row0, int Fh, const float *W, int64_t ldw, float *C, int64_t ldc, int64_t N,
+                          int K, int n, int n_members, const double *p_host, const uint64_t *seeds, int64_t mask_row0,
+                          tgcn_stream stream) {
+    using namespace tgcn;
+    const char *fn = "tgcn_embed_xw_members";
+    const EmbedH h{Eh, ldeh, Hd, ldh, h_row0, Fh};
+    MembersArgs a;
+    bool drop = false;
+    TGCN_CHECK(members_args(fn, E, lde, b, h, W, ldw, N, K, n, n_members, p_host, seeds, mask_row0, a, drop));
+    TGCN_CHECK(check_ld(fn, "ldc", ldc, int64_t(n_members) * n));
+    if (N == 0) return TGCN_OK;
+    TGCN_CHECK(members_ptrs(fn, a));
+    TGCN_CHECK(check_ptr(fn, "C", C));
+    a.s = static_cast<hipStream_t>(stream);
+    return drop ? launch_fwd_members<true>(a, C, ldc) : launch_fwd_members<false>(a, C, ldc);
+}
+
+size_t tgcn_embed_xw_members_grad_workspace_bytes(int64_t N, int K, int n, int Fh, int n_members) {
+    if (N < 0 || K <= 0 || n <= 0 || Fh < 0 || Fh > tgcn::kHMax || n_members < 1 || n_members > tgcn::kMaxMembers) return 0;
+    return tgcn::members_part_bytes(N, K, n, Fh) * static_cast<size_t>(n_members);
+}
+
+int tgcn_embed_xw_members_grad(const float *E, int64_t lde, const float *b, const float *Eh, int64_t ldeh, const float *Hd,
+                               int64_t ldh, int64_t h_row0, int Fh, const float *W, int64_t ldw, const float *G, int64_t ldg,
+                               float *dE, int64_t ldde, float *db, float *dEh, int64_t lddeh, float *dW, int64_t lddw,
+                               int64_t N, int K, int n, int n_members, const double *p_host, const uint64_t *seeds,
+                               int64_t mask_row0, void *workspace, size_t workspace_bytes, tgcn_stream stream) {
+    using namespace tgcn;
+    const char *fn = "tgcn_embed_xw_members_grad";
+    const EmbedH h{Eh, ldeh, Hd, ldh, h_row0, Fh};
+    MembersArgs a;
+    bool drop = false;
+    TGCN_CHECK(members_args(fn, E, lde, b, h, W, ldw, N, K, n, n_members, p_host, seeds, mask_row0, a, drop));
+    TGCN_CHECK(check_ld(fn, "ldg", ldg, int64_t(n_members) * n));
+    if (dE) TGCN_CHECK(check_ld(fn, "ldde", ldde, N));
+    if (a.h && dEh) TGCN_CHECK(check_ld(fn, "lddeh", lddeh, Fh));
+    if (dW) TGCN_CHECK(check_ld(fn, "lddw", lddw, n));
+    const bool db_apart = (dE == nullptr) != (db == nullptr) && N > 0;
+    if (a.h && ((dE == nullptr) != (dEh == nullptr) || db_apart)) {
+        set_error("%s: dE, db and dEh are computed together: pass all three or none (db and dEh are sums over dE)", fn);
+        return TGCN_E_INVALID;
+    }
+    if (!a.h && db_apart) {
+        set_error("%s: dE and db are computed together: pass both or neither (db is the row sum of dE)", fn);
+        return TGCN_E_INVALID;
+    }
+    a.s = static_cast<hipStream_t>(stream);
+    const int rows = n_members * K;
+    if (N == 0) {                              // empty sums; there is no element of dE
+        if (db) TGCN_HIP_CHECK(hipMemsetAsync(db, 0, sizeof(float) * rows, a.s));
+        if (a.h && dEh) TGCN_HIP_CHECK(hipMemset2DAsync(dEh, sizeof(float) * lddeh, 0, sizeof(float) * Fh, rows, a.s));
+        if (dW) TGCN_HIP_CHECK(hipMemset2DAsync(dW, sizeof(float) * lddw, 0, sizeof(float) * n, rows, a.s));
+        return TGCN_OK;
+    }
+    TGCN_CHECK(members_ptrs(fn, a));
+    TGCN_CHECK(check_ptr(fn, "G", G));
+    if (!dE && !dW) {
+        set_error("%s: dE (with %s) and dW are both NULL: nothing to compute", fn, a.h ? "db and dEh" : "db");
+        return TGCN_E_INVALID;
+    }
+    const size_t one = members_part_bytes(N, K, n, Fh), need = one * static_cast<size_t>(n_members);
+    if ((dW || (dE && a.h && h.h0 < N)) && (!workspace || workspace_bytes < need)) {
+        set_error("%s: workspace of %zu bytes, %s_workspace_bytes() asks for %zu", fn, workspace_bytes, fn, need);
+        return TGCN_E_WORKSPACE;
+    }
+    float *part = static_cast<float *>(workspace);
+    const int64_t part_stride = static_cast<int64_t>(one / sizeof(float));
+    if (dE) {
+        TGCN_CHECK(drop ? launch_grad_e_members<true>(a, G, ldg, dE, ldde, db, dEh, lddeh, part, part_stride)
+                        : launch_grad_e_members<false>(a, G, ldg, dE, ldde, db, dEh, lddeh, part, part_stride));
+    }
+    if (dW) {
+        TGCN_CHECK(drop ? launch_grad_w_members<true>(a, G, ldg, dW, lddw, part, part_stride)
+                        : launch_grad_w_members<false>(a, G, ldg, dW, lddw, part, part_stride));
+    }
+    return TGCN_OK;
 }
 
 }  // extern "C"

@@ -181,8 +181,8 @@ namespace {   // (a kernel in a header: every translation unit that launches it 
 
 // out[r, j] = sum over the slices q, in order, of part[q * slice_stride + r * row_stride + j]
 template <class T>
-__global__ __launch_bounds__(256) void k_reduce_slices(const T *__restrict__ part, int slices, int64_t slice_stride,
-                                                       int row_stride, int rows, int cols, T *__restrict__ out, int64_t ld) {
+__device__ __forceinline__ void reduce_slices(const T *__restrict__ part, int slices, int64_t slice_stride, int row_stride,
+                                              int rows, int cols, T *__restrict__ out, int64_t ld) {
     const int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x;
     if (e >= int64_t(rows) * cols) return;
     const int r = static_cast<int>(e / cols), j = static_cast<int>(e % cols);
@@ -190,6 +190,12 @@ __global__ __launch_bounds__(256) void k_reduce_slices(const T *__restrict__ par
     T s = 0;
     for (int q = 0; q < slices; ++q) s += p[q * slice_stride];
     out[int64_t(r) * ld + j] = s;
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void k_reduce_slices(const T *__restrict__ part, int slices, int64_t slice_stride,
+                                                       int row_stride, int rows, int cols, T *__restrict__ out, int64_t ld) {
+    reduce_slices(part, slices, slice_stride, row_stride, rows, cols, out, ld);
 }
 
 template <class T>

@@ -9,6 +9,7 @@ Linear's weight is [K, N + Fh] and the pre-activation gains sum_f H[i, f] weight
 (`tgcn_embed_xw_h*`); the weight's gradient is still ONE tensor of the weight's shape."""
 from __future__ import annotations
 
+import ctypes
 from typing import Optional
 
 import torch
@@ -177,3 +178,129 @@ def embed_xw(E: Tensor, b: Tensor, W: Tensor, p: float = 0.0, seed: Optional[Ten
     elif seed is None:
         seed = new_seed(E.device)
     return _EmbedXW.apply(E, b, W, p, seed, h, int(h_row0))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# M members in one call (libtgcn.so `tgcn_embed_xw_members*`): the EGCN members of a sweep cell, `crossval.CrossValEGCN`.
+# ---------------------------------------------------------------------------------------------------------------------
+MAX_MEMBERS = 64
+
+
+def _member_rates(p, M: int):
+    rates = [float(p)] * M if isinstance(p, (int, float)) else [float(v) for v in p]
+    if len(rates) != M:
+        raise ValueError(f"embed_xw_members: {len(rates)} rates for {M} members")
+    if not all(0.0 <= v < 1.0 for v in rates):
+        raise ValueError(f"embed_xw_members: every member's rate must be in [0, 1), got {rates}")
+    return tuple(rates)
+
+
+def _members_call(E: Tensor, b: Tensor, W: Tensor, M: int, h: Optional[Tensor], h_row0: int):
+    """(E, b, W, h, N, D, n, Fh, head): the operands as the kernels take them and the arguments the two calls share."""
+    E, W, b = _unit_cols(E), _unit_cols(W), b.contiguous()
+    D, n = E.size(0) // M, W.size(1)
+    if h is not None:
+        N = _require_h(E, h, h_row0)
+        h = _unit_cols(h)
+        Fh = h.size(1)
+        lde = max(E.stride(0), N + Fh)
+        hier = (E.data_ptr() + 4 * N, lde, h.data_ptr(), max(h.stride(0), Fh), h_row0, Fh)
+    else:
+        N, Fh = E.size(1), 0
+        lde = max(E.stride(0), N)
+        hier = (None, 0, None, 0, 0, 0)
+    head = (E.data_ptr(), lde, b.data_ptr(), *hier, W.data_ptr(), W.stride(0))
+    return E, b, W, h, N, D, n, Fh, head
+
+
+def _rates_array(rates):
+    return (ctypes.c_double * len(rates))(*rates)
+
+
+def embed_xw_members_forward(E: Tensor, b: Tensor, W: Tensor, n_members: int, p=0.0, seeds: Optional[Tensor] = None,
+                             out: Optional[Tensor] = None, h: Optional[Tensor] = None, h_row0: int = 0) -> Tensor:
+    """C [N, M n]: member m's columns are `embed_xw_forward` of the rows [m D, (m + 1) D) of E, b and W with `p[m]` and
+    `seeds[m]` (`seeds` None: no mask).  One launch per 256 columns of n, whatever M is.  No autograd."""
+    lib = _lib.load()
+    M = int(n_members)
+    rates = _member_rates(p, M)
+    E, b, W, h, N, D, n, Fh, head = _members_call(E, b, W, M, h, h_row0)
+    c = alloc_padded(N, M * n, E.device) if out is None else out
+    _lib.check(lib.tgcn_embed_xw_members(*head, c.data_ptr(), max(c.stride(0), M * n), N, D, n, M, _rates_array(rates),
+                                         seeds.data_ptr() if seeds is not None else None, 0, _stream_ptr(E.device)))
+    return c
+
+
+def embed_xw_members_backward(E: Tensor, b: Tensor, W: Tensor, G: Tensor, n_members: int, p=0.0,
+                              seeds: Optional[Tensor] = None, want_e: bool = True, want_w: bool = True,
+                              h: Optional[Tensor] = None, h_row0: int = 0):
+    """(dE, db, dW) of `embed_xw_members_forward` for G = dC [N, M n], stacked as E, b and W are; a pair that is not wanted
+    comes back as None.  With `h`, dE is the gradient of the whole [M D, N + Fh] weight."""
+    if not (want_e or want_w):
+        return None, None, None
+    lib = _lib.load()
+    M = int(n_members)
+    rates = _member_rates(p, M)
+    E, b, W, h, N, D, n, Fh, head = _members_call(E, b, W, M, h, h_row0)
+    G = _unit_cols(G)
+    dev = E.device
+    dE = torch.empty(M * D, N + Fh, dtype=torch.float32, device=dev) if want_e else None
+    db = torch.empty(M * D, dtype=torch.float32, device=dev) if want_e else None
+    dW = torch.empty(M * D, n, dtype=torch.float32, device=dev) if want_w else None
+    ws = torch.empty(max(lib.tgcn_embed_xw_members_grad_workspace_bytes(N, D, n, Fh, M), 16), dtype=torch.uint8, device=dev)
+    _lib.check(lib.tgcn_embed_xw_members_grad(
+        *head, G.data_ptr(), max(G.stride(0), M * n), dE.data_ptr() if want_e else None, N + Fh,
+        db.data_ptr() if want_e else None, dE.data_ptr() + 4 * N if want_e and Fh else None, N + Fh,
+        dW.data_ptr() if want_w else None, n, N, D, n, M, _rates_array(rates),
+        seeds.data_ptr() if seeds is not None else None, 0, ws.data_ptr(), ws.numel(), _stream_ptr(dev)))
+    return dE, db, dW
+
+
+class _EmbedXWMembers(torch.autograd.Function):
+    """`_EmbedXW` for M members: saves the stacked parameters, the seeds and the dense rows of H; the activation is
+    recomputed where it is needed."""
+
+    @staticmethod
+    def forward(ctx, E: Tensor, b: Tensor, W: Tensor, M: int, rates, seeds: Optional[Tensor], h: Optional[Tensor],
+                h_row0: int):
+        ctx.M, ctx.rates, ctx.h_row0 = M, rates, h_row0
+        ctx.has_seeds, ctx.has_h = seeds is not None, h is not None
+        ctx.save_for_backward(E, b, W, *([seeds] if seeds is not None else []), *([h] if h is not None else []))
+        return embed_xw_members_forward(E.detach(), b.detach(), W.detach(), M, rates, seeds, h=h, h_row0=h_row0)
+
+    @staticmethod
+    def backward(ctx, G: Tensor):
+        E, b, W = ctx.saved_tensors[:3]
+        seeds = ctx.saved_tensors[3] if ctx.has_seeds else None
+        h = ctx.saved_tensors[-1] if ctx.has_h else None
+        need = ctx.needs_input_grad
+        dE, db, dW = embed_xw_members_backward(E, b, W, G, ctx.M, ctx.rates, seeds, want_e=need[0] or need[1],
+                                               want_w=need[2], h=h, h_row0=ctx.h_row0)
+        return (dE if need[0] else None), (db if need[1] else None), dW, None, None, None, None, None
+
+
+def embed_xw_members(E: Tensor, b: Tensor, W: Tensor, n_members: int, p=0.0, seeds: Optional[Tensor] = None,
+                     h: Optional[Tensor] = None, h_row0: int = 0) -> Tensor:
+    """`embed_xw` for M = `n_members` networks of equal widths in one call, with gradients: E [M D, N] (with `h`:
+    [M D, N + Fh]), b [M D] and W [M D, n] are stacked by rows, the result is [N, M n] and member m owns its columns
+    [m n, (m + 1) n).  `p` is one rate or M rates in [0, 1) -- a member at rate 0 keeps everything -- and `seeds` an int64
+    [M] device tensor, one seed of the library's random stream per member; None with some rate > 0 draws M fresh ones from
+    torch's generator.  Member m's block of the result and of every gradient is bit for bit what `embed_xw` gives on the
+    member's rows with `p[m]` and `seeds[m:m + 1]`."""
+    _require(E, b, W)
+    M = int(n_members)
+    if not 1 <= M <= MAX_MEMBERS:
+        raise ValueError(f"embed_xw_members takes 1..{MAX_MEMBERS} members, got {n_members}")
+    if E.size(0) % M:
+        raise ValueError(f"embed_xw_members: the {E.size(0)} rows of E are not {M} equal blocks")
+    if h is not None:
+        _require_h(E, h, int(h_row0))
+        h = h.detach()
+    rates = _member_rates(p, M)
+    if max(rates) == 0.0:
+        seeds = None
+    elif seeds is None:
+        seeds = torch.empty(M, dtype=torch.int64, device=E.device).random_()
+    elif seeds.dtype != torch.int64 or seeds.shape != (M,) or seeds.device != E.device or not seeds.is_contiguous():
+        raise TypeError("embed_xw_members: seeds must be a contiguous int64 [M] tensor on the operands' device")
+    return _EmbedXWMembers.apply(E, b, W, M, rates, seeds, h, int(h_row0))

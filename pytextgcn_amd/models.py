@@ -136,6 +136,33 @@ def enable_fused_hierarchy_embedding(on: bool = True) -> bool:
     return was
 
 
+def fused_embedding_admits(x, in_features: int) -> bool:
+    """The first of the two feature tests of `EGCN.takes_fused_path` (`crossval.CrossValEGCN` shares both): the fused
+    front end is on and `x` is a sparse matrix or a `hier.HierarchyFeatures` of the layer's width."""
+    held = isinstance(x, hier.HierarchyFeatures)           # [I | H] as class ids or dense rows: the type selects the product
+    return bool(_FUSED_EMBEDDING and (x.is_sparse or held) and x.size(1) == in_features)
+
+
+def fused_embedding_features(x) -> bool:
+    """The second: `x` is the sparse identity, `[I | H]` under `enable_fused_hierarchy_embedding()`, or a
+    `hier.HierarchyFeatures` within the cap."""
+    if isinstance(x, hier.HierarchyFeatures):
+        return x.n_features <= embed.max_hierarchy_features()
+    if is_sparse_identity(x):
+        return True
+    if not _FUSED_HIERARCHY:
+        return False
+    h = split_identity_block(x)
+    return h is not None and h.size(1) <= embed.max_hierarchy_features()
+
+
+def fused_embedding_operand(x):
+    """`(Hd, h_row0)` of features that pass the two tests: what `embed.embed_xw` takes as `h`, `h_row0`."""
+    if isinstance(x, hier.HierarchyFeatures):
+        return x.dense_block(), x.h_row0
+    return (None, 0) if x.size(0) == x.size(1) else dense_hierarchy_block(split_identity_block(x))
+
+
 class EmbeddingLinear(nn.Linear):
     """`layers[0]` of EGCN: torch's `nn.Linear` (same parameters, same init, same state_dict keys) whose forward runs on
     this package's kernels for every feature format of text2graph.py:226-246 -- `features_times` on `weight.t()`, plus
@@ -183,19 +210,11 @@ class EGCN(nn.Module):
     def takes_fused_path(self, x) -> bool:
         """Whether `forward` on the features `x` runs the fused embedding product (see the class docstring)."""
         p = float(self.dropout)
-        held = isinstance(x, hier.HierarchyFeatures)       # [I | H] as class ids or dense rows: the type selects the product
-        if not (_FUSED_EMBEDDING and (x.is_sparse or held) and x.size(1) == self.layers[0].in_features):
+        if not fused_embedding_admits(x, self.layers[0].in_features):
             return False
         if self.training and p != 0.0 and not (_FUSED_DROPOUT and 0.0 < p < 1.0):
             return False
-        if held:
-            return x.n_features <= embed.max_hierarchy_features()
-        if is_sparse_identity(x):
-            return True
-        if not _FUSED_HIERARCHY:
-            return False
-        h = split_identity_block(x)
-        return h is not None and h.size(1) <= embed.max_hierarchy_features()
+        return fused_embedding_features(x)
 
     def forward(self, g):
         x = g.x
@@ -203,10 +222,7 @@ class EGCN(nn.Module):
         if self.takes_fused_path(x):
             _require_cuda(x, "g.x")
             plan = first.plan(x, g.edge_index, g.edge_attr)
-            if isinstance(x, hier.HierarchyFeatures):
-                hd, h_row0 = x.dense_block(), x.h_row0
-            else:
-                hd, h_row0 = (None, 0) if x.size(0) == x.size(1) else dense_hierarchy_block(split_identity_block(x))
+            hd, h_row0 = fused_embedding_operand(x)
             xw = embed.embed_xw(emb.weight, emb.bias, first.weight, float(self.dropout) if self.training else 0.0,
                                 h=hd, h_row0=h_row0)
             x = propagate(plan, xw, first.bias)

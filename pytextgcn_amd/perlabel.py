@@ -338,7 +338,49 @@ class BlockDiagonalConv(nn.Module):
         return f"{self.__class__.__name__}({self.n_hidden}, {list(self.class_counts)})"
 
 
-class PerLabelGCN(nn.Module):
+class MemberDropoutXW:
+    """The dropout of the propagated [N, K h] activation and its product with the block-diagonal layer-2 weight, for the
+    networks of K members (`PerLabelGCN`, `crossval.CrossValGCN`, `crossval.CrossValEGCN`).  It reads these and nothing else
+    of the network: `dropout` (a float, or a tuple of K rates), `n_groups`, `n_hidden`, `seg_start`, `seg_width` and
+    `training`."""
+
+    def _dropout_xw(self, x: Tensor, weight: Tensor) -> Tensor:
+        """dropout(H1cat) blockdiag(W2) under the class's dropout rules (`crossval.CrossValEGCN` runs it as well)."""
+        if isinstance(self.dropout, tuple):
+            return self._xw_member_rates(x, weight)
+        if models._FUSED_DROPOUT and self.training and 0.0 < float(self.dropout) < 1.0:
+            seeds = torch.empty(self.n_groups, dtype=torch.int64, device=x.device).random_()
+            return block_diag_xw(x, weight, self.seg_start, self.seg_width, float(self.dropout), seeds)
+        x = nn.functional.dropout(x, p=self.dropout, training=self.training)
+        return block_diag_xw(x, weight, self.seg_start, self.seg_width)
+
+    def _xw_member_rates(self, x: Tensor, weight: Tensor) -> Tensor:
+        """dropout(H1cat) blockdiag(W2) with a rate per member (`self.dropout` is a tuple)."""
+        rates, h = self.dropout, self.n_hidden
+        if not self.training or max(rates) == 0.0:
+            return block_diag_xw(x, weight, self.seg_start, self.seg_width)
+        if models._FUSED_DROPOUT:
+            seeds = torch.empty(self.n_groups, dtype=torch.int64, device=x.device).random_()
+            return block_diag_xw(x, weight, self.seg_start, self.seg_width, rates, seeds)
+        # torch's stream: F.dropout per column block with its rate (K small launches and one concatenation)
+        x = torch.cat([nn.functional.dropout(x[:, k * h:(k + 1) * h], p=p, training=True) for k, p in enumerate(rates)], 1)
+        return block_diag_xw(x, weight, self.seg_start, self.seg_width)
+
+    def member_dropout(self, k: int) -> float:
+        """The dropout rate of member k."""
+        return self.dropout[k] if isinstance(self.dropout, tuple) else self.dropout
+
+    @staticmethod
+    def _rates_of(members, dropout):
+        """`from_members`' rule: `dropout` when it is given; else the members' rates -- a float when they are all equal,
+        the K rates when they differ."""
+        if dropout is not None:
+            return dropout
+        rates = [m.dropout for m in members]
+        return rates[0] if all(r == rates[0] for r in rates) else rates
+
+
+class PerLabelGCN(MemberDropoutXW, nn.Module):
     """The K two-layer `GCN(in_channels, C_k, n_hidden_gcn=h, dropout=...)` of perlabel_amazon.py:113 as one network
     (module docstring).  `n_gcn` other than 2, an activation and `ShardedGCN` are out of scope.  `dropout` is one rate for
     all members (a float) or K rates in [0, 1), one per member.
@@ -396,43 +438,11 @@ class PerLabelGCN(nn.Module):
         the rows that will be read; the last propagate step runs on the operator restricted to them, as in `GCN`."""
         first, second = self.layers
         x = first(g.x, g.edge_index, g.edge_attr)
-        if isinstance(self.dropout, tuple):
-            xw = self._xw_member_rates(x, second.weight)
-        elif models._FUSED_DROPOUT and self.training and 0.0 < float(self.dropout) < 1.0:
-            seeds = torch.empty(self.n_groups, dtype=torch.int64, device=x.device).random_()
-            xw = block_diag_xw(x, second.weight, self.seg_start, self.seg_width, float(self.dropout), seeds)
-        else:
-            x = nn.functional.dropout(x, p=self.dropout, training=self.training)
-            xw = block_diag_xw(x, second.weight, self.seg_start, self.seg_width)
+        xw = self._dropout_xw(x, second.weight)
         plan = first.plan(g.x, g.edge_index, g.edge_attr)
         if rows is not None:
             plan = plan.on_rows(rows) or plan
         return propagate(plan, xw, second.bias)
-
-    def _xw_member_rates(self, x: Tensor, weight: Tensor) -> Tensor:
-        """dropout(H1cat) blockdiag(W2) with a rate per member (`self.dropout` is a tuple)."""
-        rates, h = self.dropout, self.n_hidden
-        if not self.training or max(rates) == 0.0:
-            return block_diag_xw(x, weight, self.seg_start, self.seg_width)
-        if models._FUSED_DROPOUT:
-            seeds = torch.empty(self.n_groups, dtype=torch.int64, device=x.device).random_()
-            return block_diag_xw(x, weight, self.seg_start, self.seg_width, rates, seeds)
-        # torch's stream: F.dropout per column block with its rate (K small launches and one concatenation)
-        x = torch.cat([nn.functional.dropout(x[:, k * h:(k + 1) * h], p=p, training=True) for k, p in enumerate(rates)], 1)
-        return block_diag_xw(x, weight, self.seg_start, self.seg_width)
-
-    def member_dropout(self, k: int) -> float:
-        """The dropout rate of member k."""
-        return self.dropout[k] if isinstance(self.dropout, tuple) else self.dropout
-
-    @staticmethod
-    def _rates_of(members, dropout):
-        """`from_members`' rule: `dropout` when it is given; else the members' rates -- a float when they are all equal,
-        the K rates when they differ."""
-        if dropout is not None:
-            return dropout
-        rates = [m.dropout for m in members]
-        return rates[0] if all(r == rates[0] for r in rates) else rates
 
     def loss(self, g, target, mask, group, counts=None, return_pred=False, route=None, class_map=None, rows=None):
         """`grouped_masked_cross_entropy` of `self(g, rows)`: `(loss, loss_k[, pred])`."""
