@@ -3,8 +3,10 @@
 pure-Python restatement of what the two launchers choose, and the operands the kernel tests share.  CPU only.  Test
 infrastructure; nothing under pytextgcn_amd/ imports this.
 
-The restated choices are written from `tgcn_member_ce` and `adam_members_impl`; they exist so that the tests can say "every
-leaf, one case past each launch cap" about their case lists -- no test asks them what the right answer is."""
+The restated choices are written from `tgcn_member_ce` and `adam_members_impl` (csrc/crossval.hip) with what they share with
+the flat kernels: `ce_dispatch` / `ce_grid` / `ce_v4` (csrc/masked_ce.h) and `adam_launch` (csrc/adam.h).  They exist so that
+the tests can say "every leaf, one case past each launch cap" about their case lists -- no test asks them what the right
+answer is."""
 import zlib
 from functools import lru_cache
 
@@ -16,23 +18,25 @@ import _train_cases as tc
 FILL = 7.0                                      # what every output buffer holds before a call
 
 # ---- tgcn_member_ce: the launcher's choice ---------------------------------------------------------------------------
-MCE_BLOCKS, MCE_MIN_BLOCKS = 2048, 32           # crossval.hip: kMceBlocks, kMceMinBlocks
+MCE_BLOCKS, MCE_MIN_BLOCKS = 2048, 32           # crossval.hip: `kMceBlocks = 2048`, `kMceMinBlocks = 32`
 
 
 def mce_cap(K):
-    """`mce_cap`: the workgroups per member of one launch, max(kMceMinBlocks, kMceBlocks / K)"""
+    """`mce_cap` (crossval.hip), tgcn_member_ce's cap for ce_grid: `std::max(kMceMinBlocks, kMceBlocks / K)` workgroups per member"""
     return max(MCE_MIN_BLOCKS, MCE_BLOCKS // K)
 
 
 def mce_leaf(C):
-    """(LPR, KPL, rows_per_block) by class count: the TGCN_MCE chain of tgcn_member_ce, which is masked_ce_impl's"""
+    """(LPR, KPL, rows_per_block) by class count: `ce_dispatch` / `ce_grid` of csrc/masked_ce.h, the one table tgcn_member_ce
+    and masked_ce_impl both call"""
     lpr, kpl, _, rpb = tc.ce_leaf(C, False)
     return lpr, kpl, rpb
 
 
 def mce_v4(S, ld, ldd, off, offd, has_grad):
-    """`v4 = S % 4 == 0 && ld % 4 == 0 && logits % 16 == 0 && (!dlogits || (ldd % 4 == 0 && dlogits % 16 == 0))` for buffers
-    that start `off` / `offd` floats into a 16-byte aligned allocation -- whatever C is"""
+    """`ce_v4(S, logits, ld, dlogits, ldd)` (csrc/masked_ce.h, called by tgcn_member_ce with width = S): `width % 4 == 0 &&
+    ld % 4 == 0 && logits % 16 == 0 && (!dlogits || (ldd % 4 == 0 && dlogits % 16 == 0))` for buffers that start `off` /
+    `offd` floats into a 16-byte aligned allocation -- whatever C is"""
     return S % 4 == 0 and ld % 4 == 0 and off % 4 == 0 and (not has_grad or (ldd % 4 == 0 and offd % 4 == 0))
 
 
@@ -44,7 +48,7 @@ def mce_rows_past_cap(K, C):
 LEAF_C = {(4, 4): 5, (4, 8): 17, (8, 8): 33, (16, 8): 65, (32, 8): 129, (64, 4): 257}     # one class count per leaf
 
 # ---- tgcn_adam_members: the launcher's choice ------------------------------------------------------------------------
-ADAM_CAP = tc.ADAM_CAP                          # adam_members_impl: `grid = min(8192, (n / 4 + 255) / 256 + 1)`, as adam_impl
+ADAM_CAP = tc.ADAM_CAP                          # adam_launch (csrc/adam.h), for adam_members_impl as for adam_impl
 
 
 def adam_members_v4(width, n_cols):

@@ -1,9 +1,11 @@
 """Cases of the sweep over the training-step kernels of csrc/train.hip (tests/test_gpu_train_kernels.py): the masked
-cross-entropy (k_masked_ce + k_ce_final), Adam (k_adam + k_adam_scalars) and k_scale_unless_one.  The case lists, a
+cross-entropy (k_masked_ce + k_ce_final; row body and leaf table in csrc/masked_ce.h), Adam (k_adam + k_adam_scalars; sweep
+and launcher in csrc/adam.h) and k_scale_unless_one.  The case lists, a
 pure-Python restatement of what the launchers choose, the inputs and the float64 references.  CPU only: numpy; nothing here
 imports torch.cuda or the library.  Test infrastructure; tests/test_train_cases.py keeps the lists honest.
 
-The restated choices are written from `masked_ce_impl` and `adam_impl`; the lines are cited where they are restated.  They
+The restated choices are written from `masked_ce_impl` (csrc/train.hip) with `ce_dispatch` / `ce_grid` / `ce_v4`
+(csrc/masked_ce.h) and from `adam_launch` (csrc/adam.h); the lines are cited where they are restated.  They
 exist so that the host test can say "every leaf, both sides of every boundary, one case above each launch cap" about the
 LIST -- the GPU test never asks them what the right answer is."""
 import zlib
@@ -16,19 +18,19 @@ FILL = 7.0                                      # what every output buffer holds
 N_SMALL = 257                                   # rows of the small cases: five row groups of the widest leaf, one ragged
 
 # ---- masked cross-entropy: the launcher's choice ---------------------------------------------------------------------
-CE_BLOCKS = 2048                                # train.hip: `constexpr int kCeBlocks = 2048`
+CE_BLOCKS = 2048                                # train.hip: `constexpr int kCeBlocks = 2048` (masked_ce_impl's cap for ce_grid)
 CE_EDGES = ((16, 17), (32, 33), (64, 65), (128, 129), (256, 257))
 CE_RANGES = ((1, 16), (17, 32), (33, 64), (65, 128), (129, 256), (257, None))
 
 
 def ce_leaf(C, v4):
-    """(LPR, KPL, in_regs, rows_per_block) of `masked_ce_impl` (csrc/train.hip) for C classes.
+    """(LPR, KPL, in_regs, rows_per_block) of `ce_dispatch` / `ce_grid` (csrc/masked_ce.h) for C classes.
 
-    `constexpr int kpl = 8; if (kpl == 8 && C > 16 && C <= 256) { ... C <= 32: TGCN_CE(4, 8), C <= 64: TGCN_CE(8, 8),
-    C <= 128: TGCN_CE(16, 8), else TGCN_CE(32, 8) } else if (C <= 16) TGCN_CE(4, 4); ... else TGCN_CE(64, 4);` -- with
-    kpl == 8 the middle of the second chain is dead and C > 256 falls through to (64, 4).  `rows_per_block = 2 * 4 * (...)`
-    is UN = 2 row groups x 4 waves x (64 / LPR) rows; `in_regs = C <= KPL * LPR` is k_masked_ce's own test.  `v4` (the
-    TGCN_CE macro's `if (v4)`) picks the column map, not the tuple; it is an argument so that a leaf is (C range, v4)."""
+    `if (C <= 16) leaf(4, 4); else if (C <= 32) leaf(4, 8); else if (C <= 64) leaf(8, 8); else if (C <= 128) leaf(16, 8);
+    else if (C <= 256) leaf(32, 8); else leaf(64, 4);` (the arguments as std::integral_constant).  ce_grid's
+    `rows_per_block = 2 * 4 * (64 / lpr)` is UN = 2 row groups x 4 waves x (64 / LPR) rows; `in_regs = C <= KPL * LPR` is
+    ce_rows' own test.  `v4` (`leaf`'s `if (v4)`) picks the column map, not the tuple; it is an argument so that a leaf is
+    (C range, v4)."""
     assert C >= 1 and (not v4 or C % 4 == 0)
     if C <= 16:
         lpr, kpl = 4, 4
@@ -46,13 +48,14 @@ def ce_leaf(C, v4):
 
 
 def ce_v4(C, ld, ldd, off, offd, has_grad):
-    """`const bool v4 = C % 4 == 0 && ld % 4 == 0 && logits % 16 == 0 && (!dlogits || (ldd % 4 == 0 && dlogits % 16 == 0))`
-    (masked_ce_impl), for buffers whose base is 16-byte aligned and that start `off` / `offd` floats into it."""
+    """`ce_v4(C, logits, ld, dlogits, ldd)` (csrc/masked_ce.h, called by masked_ce_impl with width = C): `width % 4 == 0 &&
+    ld % 4 == 0 && logits % 16 == 0 && (!dlogits || (ldd % 4 == 0 && dlogits % 16 == 0))`, for buffers whose base is 16-byte
+    aligned and that start `off` / `offd` floats into it."""
     return C % 4 == 0 and ld % 4 == 0 and off % 4 == 0 and (not has_grad or (ldd % 4 == 0 and offd % 4 == 0))
 
 
 def ce_grid(C, n):
-    """`grid = min(kCeBlocks, max(1, ceil(n_rows / rows_per_block)))`"""
+    """ce_grid(n_rows, lpr, kCeBlocks): `min(cap, max(1, (n_rows + rows_per_block - 1) / rows_per_block))`"""
     rpb = ce_leaf(C, False)[3]
     return min(CE_BLOCKS, max(1, -(-n // rpb)))
 
@@ -260,10 +263,10 @@ TINY_ROW = 2.0 ** -100
 
 
 # ---- Adam ------------------------------------------------------------------------------------------------------------
-ADAM_BLOCKS = 8192                              # adam_impl: `grid = min(8192, (n / 4 + 255) / 256 + 1)`
+ADAM_BLOCKS = 8192                              # adam_launch (csrc/adam.h): `a.grid = min(8192, (n / 4 + 255) / 256 + 1)`
 ADAM_PER_BLOCK = 1024                           # 256 threads x 4 elements
 ADAM_CAP = ADAM_BLOCKS * ADAM_PER_BLOCK         # 8 388 608: above it a thread takes a second stride
-ADAM_NT = 1 << 24                               # adam_impl: `const bool nt = n >= (int64_t(1) << 24)`
+ADAM_NT = 1 << 24                               # adam_launch: `const bool nt = n >= (int64_t(1) << 24)`
 AdamCase = namedtuple("AdamCase", "n amsgrad wd beta1")
 ADAM_SMALL_N = (1, 2, 3, 5, 6, 7, 1023, 1024, 1025)
 ADAM_BETA1 = (0.9, 0.5, 0.3)
@@ -272,9 +275,9 @@ ADAM_LR, ADAM_BETA2, ADAM_EPS = 1e-3, 0.999, 1e-8
 
 
 def adam_leaf(n, amsgrad):
-    """(nt, grid) of `adam_impl` (csrc/train.hip): `grid = min(8192, (n / 4 + 255) / 256 + 1)` workgroups of 256 threads, four
-    elements per thread and stride; `nt = n >= 1 << 24` streams the state past the caches.  `amsgrad` (max_exp_avg_sq !=
-    NULL) picks the other template argument and changes neither."""
+    """(nt, grid) of `adam_launch` (csrc/adam.h), which `adam_impl` (csrc/train.hip) calls: `a.grid = min(8192, (n / 4 + 255) /
+    256 + 1)` workgroups of 256 threads, four elements per thread and stride; `nt = n >= 1 << 24` streams the state past the
+    caches.  `amsgrad` (max_exp_avg_sq != NULL) picks the other template argument and changes neither."""
     return n >= ADAM_NT, min(ADAM_BLOCKS, (n // 4 + 255) // 256 + 1)
 
 
@@ -285,7 +288,7 @@ def adam_second_stride(n, amsgrad=True):
 
 def lerp_branch(beta1):
     """which branch of adam_element's `m = w1 < 0.5f ? m + w1 * diff : gr - diff * (1.f - w1)` a beta1 takes, with
-    `w1 = static_cast<float>(1.0 - beta1)` as adam_impl derives it.  beta1 = 0.5 gives w1 = 0.5f exactly: NOT below 0.5f, the
+    `w1 = static_cast<float>(1.0 - beta1)` as adam_launch derives it.  beta1 = 0.5 gives w1 = 0.5f exactly: NOT below 0.5f, the
     second branch."""
     return "low" if np.float32(1.0 - beta1) < np.float32(0.5) else "high"
 
@@ -329,7 +332,7 @@ def adam_inputs(c):
 
 
 def adam_scalars(step, lr=ADAM_LR, beta1=0.9, beta2=ADAM_BETA2):
-    """the two step-dependent floats as adam_impl derives them on the host: `bc = 1.0 - std::pow(beta, double(step))`,
+    """the two step-dependent floats as adam_launch derives them on the host: `bc = 1.0 - std::pow(beta, double(step))`,
     `float(lr / bc1)`, `float(1.0 / std::sqrt(bc2))` -- all in double, rounded once"""
     bc1, bc2 = 1.0 - beta1 ** float(step), 1.0 - beta2 ** float(step)
     return np.float32(lr / bc1), np.float32(1.0 / np.sqrt(bc2))

@@ -217,6 +217,57 @@ def test_member_ce_second_grid_stride(cuda, leaf):
     print(f"\nmember ce stride {leaf_id(leaf)} n={n}: {check(c, out, ref)}")
 
 
+ONE_MEMBER = [(C, tc.N_SMALL) for v4 in (True, False) for C in tc.LEAF_WIDTH[v4]] + \
+             [(C, tc.CE_BLOCKS * tc.ce_leaf(C, False)[3] + 37) for C in (16, 260)]
+
+
+@pytest.mark.parametrize("C,n", ONE_MEMBER, ids=[f"C{C}-n{n}" for C, n in ONE_MEMBER])
+def test_one_member_without_pad_is_the_flat_masked_ce_bit_for_bit(cuda, C, n):
+    """K = 1, seg_stride == C, bits = mask: `tgcn_member_ce` against `tgcn_masked_ce_grad` on the same logits, targets and
+    mask -- one width per leaf of both column maps at 257 rows, and C = 16 / C = 260 one ragged row group past the launch cap
+    (mce_cap(1) == kCeBlocks: the same grid).  Both kernels are the one row body of csrc/masked_ce.h under two views, so
+    the loss, the gradient and the arg-max are the same bits, and so is the bias gradient on the register path
+    (C <= 256), where both sides reduce the workgroups' column sums in k_colsum_final's order.  Wider members: see below."""
+    lib = _lib.load()
+    assert R.mce_cap(1) == tc.CE_BLOCKS
+    inp = tc.ce_inputs(C, n, "randn")
+    logits = torch.from_numpy(inp["x"]).to(cuda)
+    target = torch.from_numpy(inp["target"]).to(cuda)
+    mask = torch.from_numpy(inp["mask"].astype(np.uint8)).to(cuda)
+    assert logits.data_ptr() % 16 == 0
+    stream = plan_mod._stream_ptr(cuda)
+    new = lambda *shape, dtype=F32: torch.full(shape, R.FILL, dtype=dtype, device=cuda)
+    # the flat kernel
+    f_loss, f_d, f_db, f_pred = new(1), new(n, C), new(C), new(n, dtype=I64)
+    ws_bytes = lib.tgcn_masked_ce_grad_workspace_bytes(n, C)
+    ws = torch.empty(ws_bytes + 16, dtype=torch.uint8, device=cuda)
+    assert lib.tgcn_masked_ce_grad(logits.data_ptr(), C, n, C, target.data_ptr(), mask.data_ptr(), ctypes.c_float(inp["inv_count"]),
+                                   f_loss.data_ptr(), f_d.data_ptr(), C, f_db.data_ptr(), f_pred.data_ptr(), ws.data_ptr(),
+                                   ws_bytes, stream) == _lib.OK, lib.tgcn_last_error()
+    # one member, no pad
+    m_loss, m_loss_k, m_d, m_db, m_pred = new(1), new(1), new(n, C), new(C), new(n, 1, dtype=torch.int32)
+    inv = torch.tensor([inp["inv_count"]], dtype=F32, device=cuda)
+    bits = mask.to(I64)                                                # uint64 words: bit 0 is the mask
+    ws_bytes = lib.tgcn_member_ce_workspace_bytes(n, 1, C)
+    ws = torch.empty(ws_bytes + 16, dtype=torch.uint8, device=cuda)
+    assert lib.tgcn_member_ce(logits.data_ptr(), C, n, 1, C, C, target.data_ptr(), bits.data_ptr(), inv.data_ptr(),
+                              m_loss.data_ptr(), m_loss_k.data_ptr(), m_d.data_ptr(), C, m_db.data_ptr(), m_pred.data_ptr(),
+                              ws.data_ptr(), ws_bytes, stream) == _lib.OK, lib.tgcn_last_error()
+    torch.cuda.synchronize()
+    words = lambda t: t.view(torch.int32)
+    equal = {"loss": torch.equal(words(m_loss), words(f_loss)), "loss_k": torch.equal(words(m_loss_k), words(f_loss)),
+             "dlogits": torch.equal(words(m_d), words(f_d)), "dbias": torch.equal(words(m_db), words(f_db)),
+             "pred": torch.equal(m_pred[:, 0].to(I64), f_pred)}
+    e_db = _err(m_db.cpu(), f_db.cpu())
+    print(f"\none member C={C} n={n}: bit-equal {equal}; dbias max|a - b| / max|b| = {e_db:.2e}")
+    assert bool(torch.isfinite(f_loss).all()) and float(f_d.abs().max()) > 0 and int(f_pred.max()) > 0
+    assert equal["loss"] and equal["loss_k"] and equal["dlogits"] and equal["pred"], equal
+    # Wider than 256 classes the bias gradient is a second pass over dlogits, and the two sides sum its rows in another
+    # order (launch_colsum against k_member_colsum_wide): measured before the kernels shared their body, 2.8e-7 (C = 260),
+    # 1.9e-7 (C = 257) and 2.4e-7 (C = 260 at 16 421 rows) apart, everything else bit-equal.  Held to the file's bar.
+    assert equal["dbias"] if C <= 256 else e_db <= TOL, (equal, e_db)
+
+
 def test_functional_backward_scales_and_leaves_its_notes(cuda):
     """`(loss * 2.5).backward()` through the autograd node: the gradient, the column sums found by the node that stands where
     the last propagate step stands (no second pass over dlogits), and the zero-row note with keep = bits != 0"""
