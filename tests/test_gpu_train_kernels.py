@@ -207,6 +207,14 @@ def _adam_device(cuda, arrays):
     return out
 
 
+def adam_rel_err(name, got, ref):
+    """the measure every Adam result is held to (bound: TOL), against a float64 reference: the parameter ("p") relative to
+    max(|p|, 1e-3), element by element; the state relative to max(|.|, 1) -- operands of size O(1) (|g| <= 15), where fp32's
+    6e-8 per operation leaves a factor of ten"""
+    floor = 1e-3 if name == "p" else 1.0
+    return float(((got.double() - ref).abs() / ref.abs().clamp_min(floor)).max())
+
+
 def _run_adam(lib, cuda, c, check_lerp=False):
     p, m, v, vmax, grads = tc.adam_inputs(c)
     want = tc.adam_reference(c, p, m, v, vmax, grads)
@@ -233,11 +241,7 @@ def _run_adam(lib, cuda, c, check_lerp=False):
         if name == "vmax" and not c.amsgrad:
             assert torch.equal(got[:c.n], torch.from_numpy(first))                  # not an operand without amsgrad
             continue
-        ref = torch.from_numpy(ref)
-        # the parameter: relative to max(|p|, 1e-3), element by element; the state relative to max(|.|, 1) -- operands
-        # of size O(1) (|g| <= 15), where fp32's 6e-8 per operation leaves a factor of ten
-        floor = 1e-3 if name == "p" else 1.0
-        e = float(((got[:c.n].double() - ref).abs() / ref.abs().clamp_min(floor)).max())
+        e = adam_rel_err(name, got[:c.n], torch.from_numpy(ref))
         errs[name] = e
         assert e < TOL, (tc.adam_case_id(c), name, e)
     return errs
