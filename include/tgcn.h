@@ -870,6 +870,48 @@ int tgcn_adam_step_capturable(float *param, const float *grad, float *exp_avg, f
                               double eps, double weight_decay, int64_t *step_dev, float *scalars_dev,
                               tgcn_stream stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * tgcn_foldin_two_layer -- the logits of documents that are NOT nodes of the training graph, from tables frozen out of a
+ * trained two-layer network.  No counterpart in the reference: its Text2GraphTransformer has fit_transform
+ * only and test documents must be nodes of the graph (flat_amazon.py:57-71).  A new document d is added with edges
+ * word -> d only, weighted by its TF-IDF row, plus PyG's self loop: gcn_norm sums the degree at the TARGET, so no old node's
+ * degree, weight or activation changes and d's row of the two-layer forward is a closed form.  For document d with the
+ * entries (w_j, t_j), j in CSR order (rowptr int64 [n_docs + 1], col int32, val fp32):
+ *     deg_d = (sum_j t_j) + 1     degree_sum = TGCN_DEGREE_REFERENCE: ONE fp32 accumulator, j in order, the loop's 1.0 last;
+ *                                 TGCN_DEGREE_ACCURATE: float64 sum (lane j % 64 sums its entries in order, then a butterfly
+ *                                 over the 64 partial sums, distances 32 .. 1) + 1.0, rounded to fp32 once
+ *     dis_d = 1.0f / sqrtf(deg_d) (correctly rounded; inf -> 0)
+ *     a_j   = (dis[w_j] * t_j) * dis_d   (reference)      t_j * (dis[w_j] * dis_d)   (accurate)      a_dd = dis_d * dis_d
+ *     u     = act( sum_j a_j T1[w_j, 0:h]  +  a_dd s1  +  b1 )                                  -> hidden[d, 0:h]
+ *     z     =      sum_j a_j P[w_j, 0:C]   +  a_dd (u W2)  +  b2                                -> logits[d, 0:C]
+ * with every sum over j in CSR order from zero (one fused multiply-add per term), u W2 summed over k = 0 .. h-1 in order,
+ * and the three terms of u and of z added left to right.  Duplicate columns add up; a document without entries has deg 1.
+ *   dis  fp32 [n_vocab]   deg^-1/2 of the word nodes of the TRAINING graph (tgcn_gcn_norm in the same degree_sum)
+ *   T1   [n_vocab, h] stride ldt1   word rows of the operand the first GCNConv propagates (x W1)
+ *   s1   [h] or NULL (= zeros)      a new document's own row of that operand;   b1 [h], b2 [C] the biases
+ *   P    [n_vocab, C] stride ldp    word rows of H1 W2, H1 the eval-mode output of the first layer after its activation
+ *   W2   [h, C] stride ldw2;  act   TGCN_ACT_NONE / TGCN_ACT_RELU
+ *   logits [n_docs, C] stride ldl;  pred int32 [n_docs] or NULL: the first arg-max of the row, as tgcn_masked_ce_pred breaks
+ *   ties;  hidden [n_docs, h] stride ldh or NULL.  Nothing outside columns [0, C) / [0, h) of a row is written.
+ * A document's result depends on its own row and the tables only -- not on the batch, its size or the position in it; no
+ * atomics.  An entry whose column lies outside [0, n_vocab) is skipped in the two sums over j on the device (it still counts
+ * in deg_d); rowptr is trusted.  One launch: a wavefront per document, TGCN_FOLDIN_DOCS_PER_WORKGROUP documents per workgroup
+ * pass (at most TGCN_FOLDIN_WORKGROUP_CAP workgroups walk the batch), W2 in LDS, column ids and weights handed out through
+ * v_readlane, 16-byte row loads.  Needs no plan, no workspace and no synchronisation; only enqueues on `stream` (legal under
+ * HIP-graph capture).  TGCN_E_INVALID before anything is enqueued for h outside 1..tgcn_foldin_max_hidden() (256), C outside
+ * 1..tgcn_foldin_max_classes() (128), n_vocab outside 1..2^31-1, n_docs < 0, a leading dimension below its width or not a
+ * multiple of 4, an unknown act / degree_sum, and (n_docs > 0) a NULL pointer other than s1 / pred / hidden or a table,
+ * bias or output that is not 16-byte aligned.  n_docs == 0 launches nothing.  Additive to ABI 7. */
+#define TGCN_FOLDIN_DOCS_PER_WORKGROUP 16
+#define TGCN_FOLDIN_WORKGROUP_CAP 512
+int tgcn_foldin_max_hidden(void);
+int tgcn_foldin_max_classes(void);
+int tgcn_foldin_two_layer(int64_t n_docs, const int64_t *rowptr, const int32_t *col, const float *val, int64_t n_vocab,
+                          const float *dis, int degree_sum, const float *T1, int64_t ldt1, int h, const float *s1,
+                          const float *b1, int act, const float *P, int64_t ldp, int C, const float *W2, int64_t ldw2,
+                          const float *b2, float *logits, int64_t ldl, int32_t *pred, float *hidden, int64_t ldh,
+                          tgcn_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -194,6 +194,11 @@ SIGNATURES = {
                                   c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "tgcn_jk_input_grad": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                    c_int64, c_int64, c_int, c_void_p]),
+    "tgcn_foldin_max_hidden": (c_int, []),
+    "tgcn_foldin_max_classes": (c_int, []),
+    "tgcn_foldin_two_layer": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64, c_int,
+                                      c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p,
+                                      c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     "tgcn_wwedges_create": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p,
                                     POINTER(c_void_p)]),
     "tgcn_wwedges_query": (c_int, [c_void_p, c_int, POINTER(c_int64)]),

@@ -1,0 +1,276 @@
+"""Fold-in: the logits of documents that are NOT nodes of the training graph, from a trained two-layer network.
+
+The reference cannot do this: its `Text2GraphTransformer` has `fit_transform` only and test documents must be nodes of the
+training graph (flat_amazon.py:57-71).  The arithmetic is exact, not an approximation: PyG's `gcn_norm`
+sums the degree at the TARGET of an edge, so a new document d added with edges word -> d only (weighted by its TF-IDF row,
+plus PyG's self loop) changes no word's or old document's degree, normalised weight or activation, and d's row of the
+two-layer forward is a closed form over tables frozen from the trained model (`tgcn_foldin_two_layer`, include/tgcn.h):
+
+    u = act( sum_j a_j T1[w_j] + a_dd s1 + b1 ),     z = sum_j a_j P[w_j] + a_dd (u W2) + b2
+
+  * `extended_graph(g, tfidf)` is that definition as a graph: what the reference arithmetic is run on in the tests;
+  * `FoldIn(model, g)` freezes dis, T1, s1, P, W2 and the biases with one eval forward and serves batches through one
+    kernel launch: no plan, no sort, no synchronisation, shape-static (legal under HIP-graph capture);
+  * `enable_fused_foldin(False)` composes the same definition from the package's other kernels (a plan per batch, two SpMMs,
+    a dense product), for A/B runs and as a second implementation in the tests.
+"""
+from __future__ import annotations
+
+from typing import Tuple
+
+import numpy as np
+import torch
+from torch import Tensor, nn
+
+from . import _lib, dense, embed, hier
+from .conv import is_sparse_identity, propagate, split_identity_block
+from .data import Data
+from .plan import GraphPlan, _require_cuda, _stream_ptr, gcn_norm_factors
+
+# On by default: one launch of the fused kernel per batch.  Off: the composition (see the module docstring).
+_FUSED_FOLDIN = True
+
+
+def enable_fused_foldin(on: bool = True) -> bool:
+    """Returns the previous setting."""
+    global _FUSED_FOLDIN
+    was, _FUSED_FOLDIN = _FUSED_FOLDIN, bool(on)
+    return was
+
+
+def _host_csr(tfidf, n_vocab: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(rowptr int64, col int32, val float32) of a scipy sparse matrix [B, n_vocab], checked on the host."""
+    from scipy import sparse as sp
+    if not sp.issparse(tfidf):
+        raise TypeError(f"expected a scipy sparse matrix [n_docs, {n_vocab}] (Text2GraphTransformer.transform) or device "
+                        f"tensors (rowptr int64, col int32, val float32), got {type(tfidf).__name__}")
+    m = tfidf.tocsr()
+    if m.shape[1] != n_vocab:
+        raise ValueError(f"the TF-IDF matrix has {m.shape[1]} columns, the training graph has {n_vocab} words")
+    if m.nnz and (int(m.indices.min()) < 0 or int(m.indices.max()) >= n_vocab):
+        raise IndexError(f"column ids must lie in [0, {n_vocab})")
+    return (np.ascontiguousarray(m.indptr, dtype=np.int64), np.ascontiguousarray(m.indices, dtype=np.int32),
+            np.ascontiguousarray(m.data, dtype=np.float32))
+
+
+def extended_graph(g, tfidf) -> Data:
+    """The training graph `g` plus one node per row of `tfidf` (scipy sparse [B, g.n_vocab]), each with the edges word -> new
+    document of its row, appended after g's edges in CSR order; no edge leaves a new node and PyG adds its self loop.  `x`
+    keeps its columns and gains B empty rows (the sparse identity becomes [N + B, N]); masks and `y` are extended with
+    False / 0.  On g's device, host or GPU.  Running the reference arithmetic on it leaves every old row as it was and
+    gives the new documents' logits: the definition `FoldIn` evaluates in closed form."""
+    n_vocab = int(g.n_vocab)
+    rowptr, col, val = _host_csr(tfidf, n_vocab)
+    B = rowptr.shape[0] - 1
+    N = g.x.size(0)
+    dev = g.edge_index.device
+    doc = np.repeat(np.arange(B, dtype=np.int64), np.diff(rowptr)) + N
+    new_index = torch.from_numpy(np.stack([col.astype(np.int64), doc])).to(dev)
+    edge_index = torch.cat([g.edge_index.long(), new_index], dim=1)
+    edge_attr = g.edge_attr
+    if edge_attr is None:
+        edge_attr = torch.ones(g.edge_index.size(1), dtype=torch.float32, device=dev)
+    edge_attr = torch.cat([edge_attr.reshape(-1).float(), torch.from_numpy(val).to(dev)])
+    x = g.x
+    if isinstance(x, hier.HierarchyFeatures):
+        x = x.to_sparse()
+    if x.is_sparse:
+        xc = x if x.is_coalesced() else x.coalesce()
+        x = torch.sparse_coo_tensor(xc.indices(), xc.values(), (N + B, x.size(1))).coalesce()
+    else:
+        x = torch.cat([x, x.new_zeros(B, x.size(1))])
+    out = Data(x=x, edge_index=edge_index, edge_attr=edge_attr, n_vocab=n_vocab)
+    if g.y is not None:
+        out.y = torch.cat([g.y, g.y.new_zeros(B)])
+    for name in ("train_mask", "val_mask", "test_mask"):
+        m = getattr(g, name, None)
+        if m is not None:
+            setattr(out, name, torch.cat([m, m.new_zeros(B)]))
+    return out
+
+
+class FoldIn:
+    """`FoldIn(model, g)`: classify documents outside the training graph `g` with the trained `model` -- `models.GCN` (linear,
+    or `apply_activation=True` with `nn.ReLU`) or `models.EGCN`, two GCNConv layers, sparse identity features.  The tables
+    are frozen from the model's current parameters by one eval forward; call `refresh()` after more training.  Inputs are a
+    scipy sparse matrix [B, g.n_vocab] (`Text2GraphTransformer.transform`; shape and largest column id are checked before
+    the copy) or device tensors `(rowptr int64 [B + 1], col int32, val float32)`, which are trusted."""
+
+    def __init__(self, model, g):
+        self.model, self.g = model, g
+        self._check(model, g)
+        self.refresh()
+
+    # -- what is supported ------------------------------------------------------------------------------------------
+    @staticmethod
+    def _check(model, g) -> None:
+        from . import models as M
+        kind = type(model)
+        if kind not in (M.GCN, M.EGCN):
+            from . import crossval, perlabel, sharded          # (the classes themselves, so that a renamed one cannot slip by)
+            causes = (((crossval.CrossValGCN, crossval.CrossValEGCN, perlabel.PerLabelGCN, perlabel.PerLabelMLP),
+                       "the K-member networks"),
+                      ((sharded.ShardedGCN,), "ShardedGCN: multi-GPU models"),
+                      ((M.JumpingKnowledgeNetwork,), "JKN: the jumping-knowledge aggregation has no closed form here"),
+                      ((M.MLP,), "MLP has no graph to fold into"))
+            why = next((text for classes, text in causes if isinstance(model, classes)), "unsupported model type")
+            raise NotImplementedError(f"FoldIn takes models.GCN and models.EGCN, not {kind.__name__} ({why})")
+        convs = list(model.layers)[(1 if kind is M.EGCN else 0):]
+        if len(convs) != 2:
+            raise NotImplementedError(f"FoldIn: n_gcn != 2 (the model has {len(convs)} GCNConv layers); the closed form is "
+                                      "the two-layer network's")
+        for c in convs:
+            if not (c.add_self_loops and c.normalize) or c.improved:
+                raise NotImplementedError("FoldIn: GCNConv(add_self_loops=True, normalize=True, improved=False) only")
+        if kind is M.GCN and getattr(model, "apply_activation", False) and type(model.activation) is not nn.ReLU:
+            raise NotImplementedError(f"FoldIn: other activations than nn.ReLU are not supported "
+                                      f"({type(model.activation).__name__})")
+        x = g.x
+        if isinstance(x, hier.HierarchyFeatures):
+            raise NotImplementedError("FoldIn: [I | H] hierarchy features (HierarchyFeatures) are not supported")
+        if not x.is_sparse:
+            raise NotImplementedError("FoldIn: dense features are not supported (sparse identity features only)")
+        if not is_sparse_identity(x):
+            if split_identity_block(x) is not None:
+                raise NotImplementedError("FoldIn: [I | H] hierarchy features are not supported")
+            raise NotImplementedError("FoldIn: non-identity features are not supported (sparse identity features only)")
+        _require_cuda(x, "g.x")
+        lib = _lib.load()
+        h, C = convs[0].out_channels, convs[1].out_channels
+        if h > lib.tgcn_foldin_max_hidden() or C > lib.tgcn_foldin_max_classes():
+            raise NotImplementedError(f"FoldIn: hidden width {h} / {C} classes exceed the kernel's "
+                                      f"{lib.tgcn_foldin_max_hidden()} / {lib.tgcn_foldin_max_classes()}")
+
+    # -- the frozen tables ------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def refresh(self) -> "FoldIn":
+        """Freeze dis, T1, s1, P, W2 and the biases again from the model's current parameters (one eval forward)."""
+        from . import models as M
+        model, g = self.model, self.g
+        egcn = type(model) is M.EGCN
+        first, second = list(model.layers)[(1 if egcn else 0):]
+        V, N = int(g.n_vocab), g.x.size(0)
+        dev = g.x.device
+        plan = first.plan(g.x, g.edge_index, g.edge_attr)
+        self.degree_sum = plan.degree_sum
+        self.n_vocab, self.h, self.C = V, first.out_channels, second.out_channels
+        self.device = dev
+        was_training = model.training
+        model.eval()
+        try:
+            if egcn:
+                emb = model.layers[0]
+                if model.takes_fused_path(g.x):
+                    xw = embed.embed_xw(emb.weight, emb.bias, first.weight, 0.0)
+                else:
+                    xw = dense.xw(torch.selu(emb(g.x)), first.weight)
+                s1 = dense.xw(torch.selu(emb.bias.detach()).unsqueeze(0).contiguous(), first.weight).squeeze(0)
+                self.act = _lib.ACT_NONE
+                h1 = propagate(plan, xw, first.bias)
+            else:
+                xw, s1 = first.weight, None              # identity features: x @ W1 is W1; a new row of x is empty
+                relu = bool(getattr(model, "apply_activation", False))
+                self.act = _lib.ACT_RELU if relu else _lib.ACT_NONE
+                h1 = propagate(plan, xw, first.bias, model.activation if relu else None)
+            p = dense.xw(h1, second.weight)
+        finally:
+            model.train(was_training)
+        h, C = self.h, self.C
+        H4, C4 = (h + 3) & ~3, (C + 3) & ~3
+        # one row-padded table: a word's T1 row and P row are one contiguous read
+        tab = torch.zeros(V, H4 + C4, dtype=torch.float32, device=dev)
+        tab[:, :h] = xw.detach()[:V]
+        tab[:, H4:H4 + C] = p.detach()[:V]
+        self._tab, self.T1, self.P = tab, tab[:, :h], tab[:, H4:H4 + C]
+        self.W2 = torch.zeros(h, C4, dtype=torch.float32, device=dev)
+        self.W2[:, :C] = second.weight.detach()
+        self.s1 = None if s1 is None else s1.detach().float().clone()
+
+        def bias_of(layer, n):
+            return torch.zeros(n, dtype=torch.float32, device=dev) if layer.bias is None else layer.bias.detach().float().clone()
+        self.b1, self.b2 = bias_of(first, h), bias_of(second, C)
+        self.dis = gcn_norm_factors(g.edge_index, g.edge_attr, N, 1, self.degree_sum)[0][:V].clone()
+        return self
+
+    # -- inputs -----------------------------------------------------------------------------------------------------
+    def _device_csr(self, tfidf) -> Tuple[Tensor, Tensor, Tensor]:
+        if isinstance(tfidf, (tuple, list)) and len(tfidf) == 3 and all(torch.is_tensor(t) for t in tfidf):
+            rowptr, col, val = tfidf
+            for name, t, dt in (("rowptr", rowptr, torch.int64), ("col", col, torch.int32), ("val", val, torch.float32)):
+                _require_cuda(t, name)
+                if t.dtype != dt or t.dim() != 1 or t.device != self.device or not t.is_contiguous():
+                    raise TypeError(f"FoldIn: `{name}` must be a contiguous 1-D {dt} tensor on {self.device}")
+            if rowptr.numel() < 1 or col.numel() != val.numel():
+                raise ValueError("FoldIn: rowptr needs n_docs + 1 entries, col and val one per stored entry")
+            return rowptr, col, val
+        rowptr, col, val = _host_csr(tfidf, self.n_vocab)
+        return tuple(torch.from_numpy(a).to(self.device) for a in (rowptr, col, val))
+
+    # -- compute ----------------------------------------------------------------------------------------------------
+    def _run(self, tfidf, want_pred: bool, want_hidden: bool = False):
+        rowptr, col, val = self._device_csr(tfidf)
+        B = rowptr.numel() - 1
+        if not _FUSED_FOLDIN:
+            return self._composed(rowptr, col, val, want_pred, want_hidden)
+        h, C = self.h, self.C
+        H4, C4 = (h + 3) & ~3, (C + 3) & ~3
+        dev = self.device
+        logits = torch.empty(B, C4, dtype=torch.float32, device=dev)
+        pred = torch.empty(B, dtype=torch.int32, device=dev) if want_pred else None
+        hidden = torch.empty(B, H4, dtype=torch.float32, device=dev) if want_hidden else None
+        if col.numel() == 0:                       # (data_ptr() of an empty tensor is null)
+            col = torch.zeros(1, dtype=torch.int32, device=dev)
+            val = torch.zeros(1, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().tgcn_foldin_two_layer(
+                B, rowptr.data_ptr(), col.data_ptr(), val.data_ptr(), self.n_vocab, self.dis.data_ptr(),
+                _lib.DEGREE_SUMS[self.degree_sum], self.T1.data_ptr(), self._tab.stride(0), h,
+                self.s1.data_ptr() if self.s1 is not None else None, self.b1.data_ptr(), self.act, self.P.data_ptr(),
+                self._tab.stride(0), C, self.W2.data_ptr(), self.W2.stride(0), self.b2.data_ptr(),
+                logits.data_ptr() if B else None, C4, pred.data_ptr() if (want_pred and B) else None,
+                hidden.data_ptr() if (want_hidden and B) else None, H4, _stream_ptr(dev)))
+        return logits[:, :C], pred, (hidden[:, :h] if want_hidden else None)
+
+    def _composed(self, rowptr: Tensor, col: Tensor, val: Tensor, want_pred: bool, want_hidden: bool):
+        """The same definition from the package's other pieces: `tgcn_gcn_norm` on the bipartite word -> document edges for
+        deg_d (the plan's own sums, in edge = CSR order, the loop last), a plan of the [B, V] matrix of a_j, two SpMMs, one
+        dense product and a row scale.  Builds a plan per batch, which sorts and synchronises."""
+        B, V, dev = rowptr.numel() - 1, self.n_vocab, self.device
+        reference = self.degree_sum == "reference"
+        row = torch.repeat_interleave(torch.arange(B, device=dev), rowptr[1:] - rowptr[:-1])
+        c = col.long()
+        dis_d = gcn_norm_factors(torch.stack([c, row + V]), val, V + B, 1, self.degree_sum)[0][V:]
+        dw = self.dis[c]
+        a = (dw * val) * dis_d[row] if reference else val * (dw * dis_d[row])
+        a_dd = ((dis_d * 1.0) * dis_d).unsqueeze(1)
+        if c.numel():
+            op = GraphPlan.from_coo(row, c, a, B, V, with_transpose=False)
+            u, zg = op.spmm(self.T1), op.spmm(self.P)
+        else:
+            u = torch.zeros(B, self.h, dtype=torch.float32, device=dev)
+            zg = torch.zeros(B, self.C, dtype=torch.float32, device=dev)
+        if self.s1 is not None:
+            u = u + a_dd * self.s1
+        u = u + self.b1
+        if self.act == _lib.ACT_RELU:
+            u = torch.relu(u)
+        if B:
+            z = (zg + a_dd * dense.xw(u.contiguous(), self.W2[:, :self.C])) + self.b2
+        else:
+            z = zg
+        pred = z.argmax(dim=1).to(torch.int32) if want_pred else None
+        return z, pred, (u if want_hidden else None)
+
+    @torch.no_grad()
+    def logits(self, tfidf) -> Tensor:
+        """float32 [B, C]: row i holds what the model's eval forward gives node N + i of `extended_graph(g, tfidf)`."""
+        return self._run(tfidf, False)[0]
+
+    @torch.no_grad()
+    def predict(self, tfidf) -> Tensor:
+        """int64 [B]: the first arg-max of every row of `logits(tfidf)`, taken inside the same launch."""
+        return self._run(tfidf, True)[1].long()
+
+    def predict_text(self, t2g, docs) -> Tensor:
+        """`predict(t2g.transform(docs))` for the fitted `Text2GraphTransformer` that built `g`."""
+        return self.predict(t2g.transform(docs))

@@ -53,6 +53,35 @@ def default_degree_sum() -> str:
     return _DEGREE_SUM
 
 
+def gcn_norm_factors(edge_index: Tensor, edge_weight: Optional[Tensor], num_nodes: int, add_self_loops: int,
+                     degree_sum: str = "reference") -> Tuple[Tensor, Tensor]:
+    """(dis, loop_w): deg^-1/2 per node (in-degree at the target incl. the self loop, inf -> 0) and the
+    weight of every node's self loop, from the WHOLE edge list -- libtgcn.so `tgcn_gcn_norm`, which walks
+    the edges in bounded chunks: no whole-graph plan, no nnz-sized temporaries.  It is the routine
+    tgcn_plan_create itself runs, so the factors are bit for bit the single-device plan's.  Shared by the 1-D
+    partition (`sharded.HipEngine.gcn_norm`) and the fold-in tables (`inductive.FoldIn`)."""
+    lib = _lib.load()
+    _require_cuda(edge_index, "edge_index")
+    if edge_index.dtype != torch.int64:
+        edge_index = edge_index.long()
+    dev = edge_index.device
+    n_edges = edge_index.size(1)
+    w = None
+    if edge_weight is not None:
+        w = edge_weight.detach().reshape(-1).float().contiguous()
+    dis = torch.empty(num_nodes, dtype=torch.float32, device=dev)
+    loop_w = torch.empty(num_nodes, dtype=torch.float32, device=dev)
+    src, dst = edge_index[0], edge_index[1]
+    with torch.cuda.device(dev):
+        _lib.check(lib.tgcn_gcn_norm(
+            num_nodes, n_edges, src.data_ptr() if n_edges else None, src.stride(0) if n_edges else 1,
+            dst.data_ptr() if n_edges else None, dst.stride(0) if n_edges else 1,
+            w.data_ptr() if w is not None else None, int(add_self_loops), _lib.DEGREE_SUMS[degree_sum],
+            dis.data_ptr(), loop_w.data_ptr(),
+            dev.index if dev.index is not None else torch.cuda.current_device(), _stream_ptr(dev)))
+    return dis, loop_w
+
+
 class GraphPlan:
     """M = D^-1/2 (A + I') D^-1/2 with M[target, source], rows [row_begin, row_end), kept in HBM
     as CSR with interleaved (col, val) pairs, plus M^T unless the operator is symmetric."""

@@ -138,28 +138,8 @@ class HipEngine:
         weight of every node's self loop, from the WHOLE edge list -- libtgcn.so `tgcn_gcn_norm`, which walks
         the edges in bounded chunks: no whole-graph plan, no nnz-sized temporaries.  It is the routine
         tgcn_plan_create itself runs, so the factors are bit for bit the single-device plan's."""
-        from . import _lib
-        from .plan import _require_cuda, _stream_ptr
-        lib = _lib.load()
-        _require_cuda(edge_index, "edge_index")
-        if edge_index.dtype != torch.int64:
-            edge_index = edge_index.long()
-        dev = edge_index.device
-        n_edges = edge_index.size(1)
-        w = None
-        if edge_weight is not None:
-            w = edge_weight.detach().reshape(-1).float().contiguous()
-        dis = torch.empty(num_nodes, dtype=torch.float32, device=dev)
-        loop_w = torch.empty(num_nodes, dtype=torch.float32, device=dev)
-        src, dst = edge_index[0], edge_index[1]
-        with torch.cuda.device(dev):
-            _lib.check(lib.tgcn_gcn_norm(
-                num_nodes, n_edges, src.data_ptr() if n_edges else None, src.stride(0) if n_edges else 1,
-                dst.data_ptr() if n_edges else None, dst.stride(0) if n_edges else 1,
-                w.data_ptr() if w is not None else None, int(add_self_loops), _lib.DEGREE_SUMS[degree_sum],
-                dis.data_ptr(), loop_w.data_ptr(),
-                dev.index if dev.index is not None else torch.cuda.current_device(), _stream_ptr(dev)))
-        return dis, loop_w
+        from .plan import gcn_norm_factors           # the wrapper itself, shared with pytextgcn_amd.inductive
+        return gcn_norm_factors(edge_index, edge_weight, num_nodes, add_self_loops, degree_sum)
 
     def make_op(self, row, col, val, n_rows, n_cols):
         from .plan import GraphPlan

@@ -205,6 +205,34 @@ def word_doc_graph(n_nodes: int, n_edges: int, seed: int = 44, device="cpu", n_c
     return g
 
 
+def hold_out_documents(g: Data, n_hold: int):
+    """Take the last `n_hold` document nodes of a `word_doc_graph` OUT of the graph: returns `(g_train, tfidf, y_hold)` --
+    the graph without those nodes and every edge that touches them (same layout, sparse identity features of its own size),
+    their word -> document weights as a scipy CSR `[n_hold, n_vocab]` float32 (rows in node order, entries in edge order),
+    and their labels.  What `pytextgcn_amd.inductive.FoldIn` and `extended_graph` take as new documents."""
+    import numpy as np
+    from scipy import sparse as sp
+    N, V = g.x.size(0), int(g.n_vocab)
+    keep_n = N - n_hold
+    if not 0 < n_hold <= N - V:
+        raise ValueError(f"n_hold must lie in 1 .. {N - V} (the documents)")
+    dev = g.edge_index.device
+    src, dst = g.edge_index[0], g.edge_index[1]
+    keep = (src < keep_n) & (dst < keep_n)
+    new = (dst >= keep_n) & (src < V)                         # word -> held-out document
+    d_new, w_new, t_new = (dst[new] - keep_n).cpu().numpy(), src[new].cpu().numpy(), g.edge_attr[new].float().cpu().numpy()
+    order = np.argsort(d_new, kind="stable")
+    rowptr = np.concatenate([[0], np.cumsum(np.bincount(d_new, minlength=n_hold))])
+    tfidf = sp.csr_matrix((t_new[order].astype(np.float32), w_new[order].astype(np.int32), rowptr), shape=(n_hold, V))
+    coo = torch.stack([src[keep], dst[keep]], dim=1).contiguous()
+    ar = torch.arange(keep_n, device=dev)
+    x = torch.sparse_coo_tensor(torch.stack([ar, ar]), torch.ones(keep_n, device=dev), (keep_n, keep_n)).coalesce()
+    out = Data(x=x, edge_index=coo.T, edge_attr=g.edge_attr[keep], y=g.y[:keep_n], test_mask=g.test_mask[:keep_n],
+               val_mask=g.val_mask[:keep_n], train_mask=g.train_mask[:keep_n], n_vocab=V)
+    out.n_classes = getattr(g, "n_classes", None)
+    return out, tfidf, g.y[keep_n:]
+
+
 def power_law_graph(n_nodes: int, n_edges: int, seed: int = 44, device="cpu", alpha: float = 2.1,
                     symmetric: bool = True, n_classes: int = 0, features: str = "none") -> Data:
     """Generic power-law graph (config c5 of BASELINE.json): endpoint i drawn with probability

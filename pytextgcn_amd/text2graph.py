@@ -128,7 +128,8 @@ class Text2GraphTransformer(BaseEstimator, TransformerMixin):
         tokens, self.max_sent_len_ = _encode_input(self.input, self.n_jobs, self.cv.vocabulary_,
                                                    self.verbose, n_docs, self.max_length)
         self._say(0, "document-word edges (TF-IDF)")
-        tfidf = TfidfTransformer().fit_transform(occ).tocsr()
+        self.tfidf_ = TfidfTransformer()                    # kept: `transform` weights a new document as the corpus was
+        tfidf = self.tfidf_.fit_transform(occ).tocsr()
         tfidf.sort_indices()
         # th.nonzero of the dense matrix (text2graph.py:148) = CSR order with sorted column indices
         doc_ids = np.repeat(np.arange(n_docs, dtype=np.int64), np.diff(occ.indptr))
@@ -172,6 +173,21 @@ class Text2GraphTransformer(BaseEstimator, TransformerMixin):
                 pickle.dump(g, out)
             print(f"text2graph: graph pickled to {target}")
         return g
+
+    def transform(self, X: List[str]) -> sp.csr_matrix:
+        """The TF-IDF rows of documents that are NOT part of the fitted graph, `[len(X), n_vocabs_]` float32 CSR with sorted
+        indices: the fitted vocabulary (words outside it are dropped) and the fitted idf, float64 TF-IDF cast to float32 as
+        the document-word edge weights are (`.float()` at text2graph.py:192).  On the fitted corpus itself it returns those
+        edge weights bit for bit.  The reference has `fit_transform` only; `pytextgcn_amd.inductive.FoldIn` takes the result."""
+        if self.cv is None or getattr(self, "tfidf_", None) is None:
+            from sklearn.exceptions import NotFittedError
+            raise NotFittedError("Text2GraphTransformer.transform: call fit_transform first (it fits the vocabulary and the "
+                                 "idf weights a new document is weighted with)")
+        occ = self.cv.transform(list(X)).tocsr()
+        occ.sort_indices()
+        tfidf = self.tfidf_.transform(occ).tocsr()
+        tfidf.sort_indices()
+        return sp.csr_matrix((tfidf.data.astype(np.float32), tfidf.indices, tfidf.indptr), shape=tfidf.shape)
 
     @staticmethod
     def load_graph(save_path):
