@@ -912,6 +912,74 @@ int tgcn_foldin_two_layer(int64_t n_docs, const int64_t *rowptr, const int32_t *
                           const float *b2, float *logits, int64_t ldl, int32_t *pred, float *hidden, int64_t ldh,
                           tgcn_stream stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * tgcn_foldin_levels -- the same for the per-level strategy (perlevel_amazon.py, perlevel_dbpedia.py): L = 2
+ * or 3 two-layer networks on ONE graph, level 1 on identity features, level l >= 2 on [I_N | H] with H a document's link of
+ * the previous level's logits (C_{l-1} columns).  A new document has no identity column, so its feature row is [0 | p] and
+ * its row of the first layer's operand is p Wh, Wh = W1[N : N + C_{l-1}].  The document's scalars deg_d, dis_d, a_j, a_dd
+ * are those of tgcn_foldin_two_layer bit for bit (the same device code), computed once; for level 1
+ *     u^1 = act( sum_j a_j T1^1[w_j] + b1^1 )         z^1 = (sum_j a_j P^1[w_j] + a_dd (u^1 W2^1)) + b2^1
+ * -- tgcn_foldin_two_layer with s1 = NULL, bit for bit -- and for l >= 2
+ *     p^l = link(z^{l-1})                             fp32 [C_{l-1}]                            -> link_out[d, 0:C_{l-1}]
+ *     s^l = sum_c p^l_c Wh^l[c, :]                    c = 0 .. C_{l-1}-1 in order from zero, one FMA per term
+ *     u^l = act( (sum_j a_j T1^l[w_j] + a_dd s^l) + b1^l )                                      -> hidden[d, 0:h_l]
+ *     z^l = (sum_j a_j P^l[w_j] + a_dd (u^l W2^l)) + b2^l                                       -> logits[d, 0:C_l]
+ * with the sums over j and k and the association of the terms as stated for tgcn_foldin_two_layer (a_dd s^l enters with one
+ * FMA).  link, per level:
+ *   TGCN_FOLDIN_LINK_SOFTMAX  m = max_c z_c;  e_c = expf(z_c - m) (the accurate expf);  S = the sum of the e_c in this order,
+ *       which depends on C alone: t_i = e_i + e_{i+64} for i + 64 < C, t_i = e_i for the other i < C, t_i = 0 for
+ *       C <= i < 64 (nothing is added there for C <= 64), then the butterfly t_i <- t_i + t_{i ^ off} over all 64 i at once
+ *       for off = 32, 16, 8, 4, 2, 1;  p_c = e_c / S, a correctly rounded division.  All in fp32.
+ *   TGCN_FOLDIN_LINK_ONE_HOT  p = the one-hot of the first arg-max of z (ties as tgcn_masked_ce_pred breaks them), so that
+ *       s^l is the row Wh^l[k] itself (it is read, not summed: a non-finite entry of another row does not reach it).
+ * `table` [n_vocab, ldt] is ONE combined table: a word's row holds, for every level, the segment T1^l = W1^l[w, 0:h_l] from
+ * column t1_col on and the segment P^l = (H1^l W2^l)[w, 0:C_l] (H1^l the level's own eval-mode first layer) from column p_col
+ * on; the segments begin at multiples of 4, lie in any order and may have gaps between them.  A word's 2L rows are then one
+ * contiguous read from one row address.  Each level is one tgcn_foldin_level:  t1_col, p_col;  W2 [h, C] stride ldw2;  Wh [C_{l-1}, h] stride ldwh (level 1: ignored);  b1 [h], b2 [C];  act;
+ * link (level 1: ignored);  outputs, EACH of which may be NULL: logits [n_docs, C] stride ldl, pred int32 [n_docs] (the first
+ * arg-max), hidden [n_docs, h] stride ldh, link_out [n_docs, C_{l-1}] stride ldk (level 1: must be NULL).
+ * Nothing beyond column h_l / C_l of a segment is read and nothing outside a result row's own columns is written.
+ * One launch for all levels: a wavefront per document, TGCN_FOLDIN_DOCS_PER_WORKGROUP documents per workgroup pass, at most
+ * TGCN_FOLDIN_WORKGROUP_CAP workgroups; one pass over the document's words gathers all 2L rows (lane l holds columns
+ * 4l .. 4l+3 of each, 16-byte loads); the levels are then resolved in the wave's LDS slice against W2^l, Wh^l and the biases,
+ * which the workgroup stages in LDS once.  No atomics, no workspace, no synchronisation; enqueues on `stream` only (legal under
+ * HIP-graph capture); a document's bits do not depend on the batch.
+ * LDS: tgcn_foldin_levels_lds_bytes(L, h[], C[]) = 4 * ( sum_l r4(h_l C_l) + sum_{l>=2} C_{l-1} r4(h_l)
+ *      + (1 + TGCN_FOLDIN_DOCS_PER_WORKGROUP) * sum_l (r4(h_l) + r4(C_l)) ), r4 = rounded up to a multiple of 4: W2, Wh, the
+ * biases once, and per wave a slice that holds every level's u and z -- host
+ * arithmetic, callable without a GPU; -1 for L outside 2..3 or a width outside 1..256 / 1..128.  A need above
+ * TGCN_FOLDIN_LEVELS_LDS_LIMIT is refused.  TGCN_E_INVALID before anything is enqueued, with the cause in tgcn_last_error, for
+ * that, n_levels outside 2..3, ldt outside 4..2^31-1 or not a multiple of 4, a segment that begins off a multiple of 4 or ends
+ * beyond ldt, the size, leading-dimension, alignment and enum rules of tgcn_foldin_two_layer applied to every level, and
+ * (n_docs > 0) a NULL rowptr, col, val, dis, table, W2, b1, b2 or (l >= 2) Wh.  n_docs == 0 launches nothing.
+ * Additive to ABI 7. */
+#define TGCN_FOLDIN_LINK_SOFTMAX 0
+#define TGCN_FOLDIN_LINK_ONE_HOT 1
+#define TGCN_FOLDIN_MAX_LEVELS 3
+#define TGCN_FOLDIN_LEVELS_LDS_LIMIT 163840 /* the 160 KiB of a CU */
+typedef struct tgcn_foldin_level {
+    int64_t t1_col;
+    int64_t p_col;
+    const float *W2;
+    int64_t ldw2;
+    const float *Wh;
+    int64_t ldwh;
+    const float *b1;
+    const float *b2;
+    float *logits;
+    int64_t ldl;
+    int32_t *pred;
+    float *hidden;
+    int64_t ldh;
+    float *link_out;
+    int64_t ldk;
+    int32_t h, C, act, link;
+} tgcn_foldin_level;
+int64_t tgcn_foldin_levels_lds_bytes(int n_levels, const int32_t *h, const int32_t *C);
+int tgcn_foldin_levels(int64_t n_docs, const int64_t *rowptr, const int32_t *col, const float *val, int64_t n_vocab,
+                       const float *dis, int degree_sum, const float *table, int64_t ldt, int n_levels,
+                       const tgcn_foldin_level *levels, tgcn_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

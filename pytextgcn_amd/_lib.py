@@ -20,6 +20,18 @@ DEGREE_ACCURATE, DEGREE_REFERENCE = 0, 1                   # `degree_sum` of tgc
 ACT_NONE, ACT_RELU = 0, 1                                   # `act` of tgcn_spmm_act / tgcn_act_grad
 HIER_ONEHOT, HIER_DENSE = 0, 1                              # `form` of tgcn_hier_xw / tgcn_hier_xw_grad
 DEGREE_SUMS = {"accurate": DEGREE_ACCURATE, "reference": DEGREE_REFERENCE}
+LINK_SOFTMAX, LINK_ONE_HOT = 0, 1                           # `link` of a tgcn_foldin_level
+LINKS = {"softmax": LINK_SOFTMAX, "one_hot": LINK_ONE_HOT}
+FOLDIN_MAX_LEVELS = 3
+FOLDIN_LEVELS_LDS_LIMIT = 163840                            # TGCN_FOLDIN_LEVELS_LDS_LIMIT
+
+
+class FoldinLevel(ctypes.Structure):
+    """`tgcn_foldin_level` of include/tgcn.h."""
+    _fields_ = [("t1_col", c_int64), ("p_col", c_int64), ("W2", c_void_p), ("ldw2", c_int64),
+                ("Wh", c_void_p), ("ldwh", c_int64), ("b1", c_void_p), ("b2", c_void_p), ("logits", c_void_p), ("ldl", c_int64),
+                ("pred", c_void_p), ("hidden", c_void_p), ("ldh", c_int64), ("link_out", c_void_p), ("ldk", c_int64),
+                ("h", c_int32), ("C", c_int32), ("act", c_int32), ("link", c_int32)]
 
 (Q_N_NODES, Q_N_ROWS, Q_NNZ, Q_NNZ_T, Q_SYMMETRIC, Q_ITEMS, Q_ITEMS_T, Q_LONG_ROWS, Q_LONG_ROWS_T,
  Q_SEGMENTS, Q_SEGMENTS_T, Q_DEVICE_BYTES, Q_ROW_BEGIN, Q_HAS_TRANSPOSE, Q_N_ROWS_T, Q_HOT_ROWS,
@@ -199,6 +211,9 @@ SIGNATURES = {
     "tgcn_foldin_two_layer": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64, c_int,
                                       c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p,
                                       c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    "tgcn_foldin_levels_lds_bytes": (c_int64, [c_int, POINTER(c_int32), POINTER(c_int32)]),
+    "tgcn_foldin_levels": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64, c_int, POINTER(FoldinLevel),
+                                   c_void_p]),
     "tgcn_wwedges_create": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p,
                                     POINTER(c_void_p)]),
     "tgcn_wwedges_query": (c_int, [c_void_p, c_int, POINTER(c_int64)]),

@@ -10,21 +10,18 @@
 //   3. u = act(. + a_dd s1 + b1) goes to the wave's LDS slice (and to `hidden`), the gathered P sum next to it; then
 //      u W2 from the workgroup's LDS copy of W2: lane l owns the columns l and l + 64, k in order; z, the store, arg-max.
 // A document's arithmetic is a function of (h, C) and its own row: the leaf never depends on the batch or the row length.
+// The document scalars, the row accesses and the u W2 epilogue live in foldin.h: foldin_levels.hip runs the same code.
 // Leaves (template): TAIL = h or C is not a multiple of 4 (the last lane of a row loads and stores scalars),
 //                    WIDE = C > 64 (a second column per lane in the epilogue).
 #include <algorithm>
 #include <atomic>
-#include <climits>
 
-#include "common.h"
+#include "foldin.h"
 
 namespace tgcn {
 namespace {
 
-constexpr int kFoldWaves = TGCN_FOLDIN_DOCS_PER_WORKGROUP;
-constexpr int kFoldMaxH = 256;      // 64 lanes x 4 columns
-constexpr int kFoldMaxC = 128;      // W2 at 256 x 128 fp32 = 128 KiB of the 160 KiB of LDS, 24 KiB for the waves' slices
-static_assert(kFoldWaves * 64 <= 1024, "one workgroup");
+using namespace fold;
 
 struct FoldArgs {
     int64_t n_docs;
@@ -52,72 +49,6 @@ struct FoldArgs {
     float *hidden;
     int64_t ldh;
 };
-
-__device__ __forceinline__ int lane_i(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
-__device__ __forceinline__ float lane_f(float v, int lane) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-
-// columns c0 .. c0+3 of a row of n columns: zeros beyond n; a 16-byte load where the four exist
-template <bool TAIL>
-__device__ __forceinline__ float4 load4(const float *__restrict__ row, int c0, int n) {
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c0 + 4 <= n) {
-        v = *reinterpret_cast<const float4 *>(row + c0);
-    } else if (TAIL && c0 < n) {
-        v.x = row[c0];
-        if (c0 + 1 < n) v.y = row[c0 + 1];
-        if (c0 + 2 < n) v.z = row[c0 + 2];
-    }
-    return v;
-}
-
-template <bool TAIL>
-__device__ __forceinline__ void store4(float *__restrict__ row, int c0, int n, const float4 v) {
-    if (c0 + 4 <= n) {
-        *reinterpret_cast<float4 *>(row + c0) = v;
-    } else if (TAIL && c0 < n) {
-        row[c0] = v.x;
-        if (c0 + 1 < n) row[c0 + 1] = v.y;
-        if (c0 + 2 < n) row[c0 + 2] = v.z;
-    }
-}
-
-__device__ __forceinline__ void fma4(float4 &acc, const float a, const float4 x) {
-    acc.x = fmaf(a, x.x, acc.x);
-    acc.y = fmaf(a, x.y, acc.y);
-    acc.z = fmaf(a, x.z, acc.z);
-    acc.w = fmaf(a, x.w, acc.w);
-}
-
-__device__ __forceinline__ float act1(const float v, const int act) {
-    return (act == TGCN_ACT_RELU && v < 0.f) ? 0.f : v;       // a NaN goes through, as torch.relu does
-}
-
-// deg_d and from it dis_d, in the plan's own rules (plan.hip: k_deg_sum_seq / k_deg_sum_f64, k_deg_finish)
-__device__ __forceinline__ float doc_dis(const float *__restrict__ val, const int64_t beg, const int64_t end, const int lane,
-                                         const int reference) {
-#pragma clang fp contract(off)
-    float deg;
-    if (reference) {
-        float s = 0.f;
-        for (int64_t b = beg; b < end; b += 64) {
-            const float v = b + lane < end ? val[b + lane] : 0.f;
-            const int cnt = static_cast<int>(min(int64_t(64), end - b));
-            for (int i = 0; i < cnt; ++i) s += lane_f(v, i);
-        }
-        deg = s + 1.0f;
-    } else {
-        double s = 0.0;
-        for (int64_t j = beg + lane; j < end; j += 64) s += static_cast<double>(val[j]);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-        deg = static_cast<float>(s + 1.0);
-    }
-    float d = 1.0f / sqrtf(deg);
-    if (isinf(d)) d = 0.0f;
-    return d;
-}
 
 template <bool TAIL, bool WIDE>
 __global__ __launch_bounds__(64 * kFoldWaves) void k_foldin(const FoldArgs A) {
@@ -150,25 +81,12 @@ __global__ __launch_bounds__(64 * kFoldWaves) void k_foldin(const FoldArgs A) {
     for (int64_t d = int64_t(blockIdx.x) * kFoldWaves + wave; d < A.n_docs; d += stride) {
         const int64_t beg = A.rowptr[d], end = A.rowptr[d + 1];
         const float dd = doc_dis(A.val, beg, end, lane, reference);
-        float a_dd;
-        {
-#pragma clang fp contract(off)
-            a_dd = (dd * 1.0f) * dd;
-        }
+        const float a_dd = doc_self_weight(dd);
         float4 accT = make_float4(0.f, 0.f, 0.f, 0.f), accP = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int64_t b = beg; b < end; b += 64) {
-            int c = -1;
-            float a = 0.f;
-            if (b + lane < end) {
-#pragma clang fp contract(off)
-                const int cj = A.col[b + lane];
-                const float t = A.val[b + lane];
-                if (cj >= 0 && cj < A.n_vocab) {
-                    const float dw = A.dis[cj];
-                    a = reference ? (dw * t) * dd : t * (dw * dd);
-                    c = cj;
-                }
-            }
+            int c;
+            float a;
+            doc_entry(A.col, A.val, A.dis, A.n_vocab, b, end, lane, dd, reference, c, a);
             const int cnt = static_cast<int>(min(int64_t(64), end - b));
             const bool clean = __ballot(lane < cnt && c < 0) == 0;      // no entry of the chunk is skipped
             int i = 0;
@@ -203,10 +121,7 @@ __global__ __launch_bounds__(64 * kFoldWaves) void k_foldin(const FoldArgs A) {
         // u = act((sum + a_dd s1) + b1); columns at and beyond h are zero (zero loads, zero sums)
         float4 u = accT;
         if (A.s1) fma4(u, a_dd, s1v);
-        u.x = act1(u.x + b1v.x, A.act);
-        u.y = act1(u.y + b1v.y, A.act);
-        u.z = act1(u.z + b1v.z, A.act);
-        u.w = act1(u.w + b1v.w, A.act);
+        u = bias_act4(u, b1v, A.act);
         if (c0 < H4) *reinterpret_cast<float4 *>(us + c0) = u;
         if (c0 < C4) *reinterpret_cast<float4 *>(zs + c0) = accP;
         if (A.hidden) store4<TAIL>(A.hidden + d * A.ldh, c0, h, u);
@@ -214,29 +129,8 @@ __global__ __launch_bounds__(64 * kFoldWaves) void k_foldin(const FoldArgs A) {
         __builtin_amdgcn_wave_barrier();                 // the slice belongs to this wave: its LDS operations run in order
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
-        float y0 = 0.f, y1 = 0.f;
-        int k = 0;
-#pragma unroll 2
-        for (; k + 4 <= h; k += 4) {
-            const float4 uu = *reinterpret_cast<const float4 *>(us + k);
-            const float *r0 = w0 + k * C;
-            y0 = fmaf(uu.x, r0[0], y0);
-            y0 = fmaf(uu.y, r0[C], y0);
-            y0 = fmaf(uu.z, r0[2 * C], y0);
-            y0 = fmaf(uu.w, r0[3 * C], y0);
-            if (WIDE) {
-                const float *r1 = w1 + k * C;
-                y1 = fmaf(uu.x, r1[0], y1);
-                y1 = fmaf(uu.y, r1[C], y1);
-                y1 = fmaf(uu.z, r1[2 * C], y1);
-                y1 = fmaf(uu.w, r1[3 * C], y1);
-            }
-        }
-        for (; k < h; ++k) {
-            const float uk = us[k];
-            y0 = fmaf(uk, w0[k * C], y0);
-            if (WIDE) y1 = fmaf(uk, w1[k * C], y1);
-        }
+        float y0, y1;
+        u_times_w2<WIDE>(us, w0, w1, h, C, y0, y1);
         float z0 = -INFINITY, z1 = -INFINITY;
         float *const out = A.logits + d * A.ldl;
         if (on0) {
@@ -248,17 +142,9 @@ __global__ __launch_bounds__(64 * kFoldWaves) void k_foldin(const FoldArgs A) {
             out[lane + 64] = z1;
         }
         if (A.pred) {
-            float m = fmaxf(z0, z1);
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-            int bi = INT_MAX;
-            if (on0 && z0 == m)
-                bi = lane;
-            else if (on1 && z1 == m)
-                bi = lane + 64;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) bi = min(bi, __shfl_xor(bi, off, 64));
-            if (lane == 0) A.pred[d] = bi == INT_MAX ? 0 : bi;
+            float m;
+            const int bi = first_argmax(z0, z1, on0, on1, lane, m);
+            if (lane == 0) A.pred[d] = bi;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();                 // the next document's stores follow this one's loads
@@ -269,8 +155,6 @@ size_t foldin_lds_bytes(int h, int C) {
     const size_t H4 = (h + 3) & ~3, C4 = (C + 3) & ~3;
     return sizeof(float) * (((size_t(h) * C + 3) & ~size_t(3)) + kFoldWaves * (H4 + C4));
 }
-
-bool aligned16(const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 template <bool TAIL, bool WIDE>
 int launch_foldin(const FoldArgs &A, hipStream_t s) {

@@ -12,11 +12,15 @@ two-layer forward is a closed form over tables frozen from the trained model (`t
   * `FoldIn(model, g)` freezes dis, T1, s1, P, W2 and the biases with one eval forward and serves batches through one
     kernel launch: no plan, no sort, no synchronisation, shape-static (legal under HIP-graph capture);
   * `enable_fused_foldin(False)` composes the same definition from the package's other kernels (a plan per batch, two SpMMs,
-    a dense product), for A/B runs and as a second implementation in the tests.
+    a dense product), for A/B runs and as a second implementation in the tests;
+  * `FoldInLevels(models, graphs)` does the same for the per-level strategy (perlevel_amazon.py, perlevel_dbpedia.py; DESIGN.md
+    4.2n): level l >= 2 sees [I | H] with H the link -- softmax or one-hot -- of the level above.  A new document has no
+    identity column, so its row of the first layer's operand is H_d W1[N:], a C_{l-1} x h product that the ONE kernel
+    (`tgcn_foldin_levels`) resolves in LDS after ONE pass over the document's words for all levels.
 """
 from __future__ import annotations
 
-from typing import Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -53,11 +57,12 @@ def _host_csr(tfidf, n_vocab: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
             np.ascontiguousarray(m.data, dtype=np.float32))
 
 
-def extended_graph(g, tfidf) -> Data:
+def extended_graph(g, tfidf, hierarchy=None) -> Data:
     """The training graph `g` plus one node per row of `tfidf` (scipy sparse [B, g.n_vocab]), each with the edges word -> new
     document of its row, appended after g's edges in CSR order; no edge leaves a new node and PyG adds its self loop.  `x`
-    keeps its columns and gains B empty rows (the sparse identity becomes [N + B, N]); masks and `y` are extended with
-    False / 0.  On g's device, host or GPU.  Running the reference arithmetic on it leaves every old row as it was and
+    keeps its columns and gains B rows (the sparse identity becomes [N + B, N]) -- empty ones, or, for [I | H] features
+    (`HierarchyFeatures` or sparse), with the float32 [B, Fh] block `hierarchy` in the H columns: a new document has no
+    identity column.  Masks and `y` are extended with False / 0.  On g's device, host or GPU.  Running the reference arithmetic on it leaves every old row as it was and
     gives the new documents' logits: the definition `FoldIn` evaluates in closed form."""
     n_vocab = int(g.n_vocab)
     rowptr, col, val = _host_csr(tfidf, n_vocab)
@@ -74,9 +79,23 @@ def extended_graph(g, tfidf) -> Data:
     x = g.x
     if isinstance(x, hier.HierarchyFeatures):
         x = x.to_sparse()
+    if hierarchy is not None:
+        Fh = x.size(1) - N
+        if not x.is_sparse or Fh < 1:
+            raise ValueError("extended_graph: `hierarchy` needs [I | H] features (HierarchyFeatures or sparse [N, N + Fh])")
+        hierarchy = torch.as_tensor(hierarchy)
+        if tuple(hierarchy.shape) != (B, Fh) or hierarchy.dtype != torch.float32:
+            raise ValueError(f"extended_graph: `hierarchy` must be float32 [{B}, {Fh}], got {hierarchy.dtype} "
+                             f"{tuple(hierarchy.shape)}")
     if x.is_sparse:
         xc = x if x.is_coalesced() else x.coalesce()
-        x = torch.sparse_coo_tensor(xc.indices(), xc.values(), (N + B, x.size(1))).coalesce()
+        idx, v = xc.indices(), xc.values()
+        if hierarchy is not None:
+            hd = hierarchy.to(dev)
+            nz = torch.nonzero(hd)
+            idx = torch.cat([idx, torch.stack([nz[:, 0] + N, nz[:, 1] + N])], 1)
+            v = torch.cat([v, hd[nz[:, 0], nz[:, 1]].to(v.dtype)])
+        x = torch.sparse_coo_tensor(idx, v, (N + B, x.size(1))).coalesce()
     else:
         x = torch.cat([x, x.new_zeros(B, x.size(1))])
     out = Data(x=x, edge_index=edge_index, edge_attr=edge_attr, n_vocab=n_vocab)
@@ -274,3 +293,256 @@ class FoldIn:
     def predict_text(self, t2g, docs) -> Tensor:
         """`predict(t2g.transform(docs))` for the fitted `Text2GraphTransformer` that built `g`."""
         return self.predict(t2g.transform(docs))
+
+
+def _bias_of(layer, n: int, dev) -> Tensor:
+    return torch.zeros(n, dtype=torch.float32, device=dev) if layer.bias is None else layer.bias.detach().float().clone()
+
+
+def _r4(v: int) -> int:
+    return (v + 3) & ~3
+
+
+class FoldInLevels:
+    """`FoldInLevels(models, graphs, link="softmax")`: classify documents outside the training graph through the per-level
+    strategy.  `models` are the L = 2 or 3 trained two-layer `models.GCN` (linear, or `apply_activation=True` with `nn.ReLU`),
+    `graphs` the graphs they run on: `g` with its sparse identity features for level 1, `with_hierarchy(g, ...)` -- a
+    `HierarchyFeatures` with as many columns as the level above has classes -- for every further level, all on the same
+    edges.  Which H the old documents carry there (their true labels, or `predicted_hierarchy`) is the caller's choice: it
+    fixes the frozen P of that level.  A new document's H is `link` of its own logits one level up: "softmax", or "one_hot"
+    of the first arg-max (one value for all levels, or one per level from the second on).  Inputs are as on `FoldIn`."""
+
+    def __init__(self, models: Sequence, graphs: Sequence, link="softmax"):
+        self.models, self.graphs = list(models), list(graphs)
+        L = len(self.models)
+        links = [link] * (L - 1) if isinstance(link, str) else list(link)
+        self._check(self.models, self.graphs, links)
+        self.links = links
+        self.refresh()
+
+    # -- what is supported ------------------------------------------------------------------------------------------
+    @staticmethod
+    def _check(models, graphs, links) -> None:
+        from . import models as M
+        lib = _lib.load()
+        L = len(models)
+        if not 2 <= L <= _lib.FOLDIN_MAX_LEVELS or len(graphs) != L:
+            raise ValueError(f"FoldInLevels: 2 or {_lib.FOLDIN_MAX_LEVELS} levels, one graph per model ({L} models, "
+                             f"{len(graphs)} graphs)")
+        if len(links) != L - 1 or any(k not in _lib.LINKS for k in links):
+            raise ValueError(f"FoldInLevels: link is one of {sorted(_lib.LINKS)}, or one per level from the second on ({links})")
+        g0 = graphs[0]
+        hs, Cs = [], []
+        for l, (model, g) in enumerate(zip(models, graphs)):
+            if type(model) is not M.GCN:
+                why = {M.EGCN: "EGCN levels: a new document's embedding row is a dense product per document",
+                       M.JumpingKnowledgeNetwork: "JKN"}.get(type(model), "unsupported model type")
+                raise NotImplementedError(f"FoldInLevels: level {l + 1} is a {type(model).__name__}, every level must be a "
+                                          f"two-layer models.GCN ({why})")
+            convs = list(model.layers)
+            if len(convs) != 2:
+                raise NotImplementedError(f"FoldInLevels: level {l + 1}: n_gcn != 2 (the model has {len(convs)} GCNConv layers)")
+            for c in convs:
+                if not (c.add_self_loops and c.normalize) or c.improved:
+                    raise NotImplementedError("FoldInLevels: GCNConv(add_self_loops=True, normalize=True, improved=False) only")
+            if getattr(model, "apply_activation", False) and type(model.activation) is not nn.ReLU:
+                raise NotImplementedError(f"FoldInLevels: level {l + 1}: other activations than nn.ReLU are not supported "
+                                          f"({type(model.activation).__name__})")
+            if l > 0:
+                for name in ("edge_index", "edge_attr"):
+                    a, b = getattr(g0, name), getattr(g, name)
+                    if a is not b and (a is None or b is None or a.shape != b.shape or not torch.equal(a, b)):
+                        raise ValueError(f"FoldInLevels: level {l + 1}'s graph has another `{name}` than level 1's: the levels "
+                                         "share one graph")
+                if int(g.n_vocab) != int(g0.n_vocab):
+                    raise ValueError(f"FoldInLevels: level {l + 1}'s graph has another `n_vocab` ({g.n_vocab}) than level 1's "
+                                     f"({g0.n_vocab})")
+            x = g.x
+            N = g0.x.size(0)
+            if l == 0:
+                if isinstance(x, hier.HierarchyFeatures) or not x.is_sparse or not is_sparse_identity(x):
+                    raise NotImplementedError("FoldInLevels: level 1 takes sparse identity features")
+                _require_cuda(x, "graphs[0].x")
+            else:
+                if not isinstance(x, hier.HierarchyFeatures):
+                    raise NotImplementedError(f"FoldInLevels: level {l + 1} takes HierarchyFeatures (with_hierarchy(g, ...)), "
+                                              f"not {type(x).__name__}")
+                if x.n_features != Cs[l - 1] or x.h_row0 != int(g0.n_vocab) or x.n_nodes != N:
+                    raise ValueError(f"FoldInLevels: level {l + 1}'s HierarchyFeatures must have n_features == {Cs[l - 1]} (the "
+                                     f"classes of level {l}), h_row0 == n_vocab == {int(g0.n_vocab)} and {N} nodes; it has "
+                                     f"n_features={x.n_features}, h_row0={x.h_row0}, n_nodes={x.n_nodes}")
+                _require_cuda(x, f"graphs[{l}].x")
+            if convs[0].in_channels != x.size(1):
+                raise ValueError(f"FoldInLevels: level {l + 1}'s model takes {convs[0].in_channels} features, its graph has "
+                                 f"{x.size(1)}")
+            hs.append(convs[0].out_channels)
+            Cs.append(convs[1].out_channels)
+            if hs[l] > lib.tgcn_foldin_max_hidden() or Cs[l] > lib.tgcn_foldin_max_classes():
+                raise NotImplementedError(f"FoldInLevels: level {l + 1}: hidden width {hs[l]} / {Cs[l]} classes exceed the "
+                                          f"kernel's {lib.tgcn_foldin_max_hidden()} / {lib.tgcn_foldin_max_classes()}")
+        need = levels_lds_bytes(hs, Cs)
+        if need > _lib.FOLDIN_LEVELS_LDS_LIMIT:
+            raise NotImplementedError(f"FoldInLevels: the levels' W2 and Wh need {need} bytes of LDS next to the waves' slices, "
+                                      f"a compute unit has {_lib.FOLDIN_LEVELS_LDS_LIMIT}")
+
+    # -- the frozen tables ------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def refresh(self) -> "FoldInLevels":
+        """Freeze dis, the combined table, W2, Wh and the biases again from the models' current parameters: one eval forward
+        per level on that level's own graph."""
+        g0 = self.graphs[0]
+        V, N, dev = int(g0.n_vocab), g0.x.size(0), g0.x.device
+        self.n_vocab, self.device = V, dev
+        self.h, self.C, self.act = [], [], []
+        self.W2, self.Wh, self.b1, self.b2 = [], [], [], []
+        xws, ps = [], []
+        for l, (model, g) in enumerate(zip(self.models, self.graphs)):
+            first, second = list(model.layers)
+            plan = first.plan(g.x, g.edge_index, g.edge_attr)
+            if l == 0:
+                self.degree_sum = plan.degree_sum
+            relu = bool(getattr(model, "apply_activation", False))
+            was_training = model.training
+            model.eval()
+            try:
+                xw = first.features_times(g.x, first.weight)             # W1 itself, or hier.xw on [I | H]
+                h1 = propagate(plan, xw, first.bias, model.activation if relu else None)
+                ps.append(dense.xw(h1, second.weight).detach()[:V])
+            finally:
+                model.train(was_training)
+            h, C = first.out_channels, second.out_channels
+            xws.append(first.weight.detach()[:V])                         # word rows have H = 0: their row of x W1 is W1's
+            self.h.append(h), self.C.append(C), self.act.append(_lib.ACT_RELU if relu else _lib.ACT_NONE)
+            w2 = torch.zeros(h, _r4(C), dtype=torch.float32, device=dev)
+            w2[:, :C] = second.weight.detach()
+            self.W2.append(w2)
+            wh = None
+            if l > 0:
+                wh = torch.zeros(self.C[l - 1], _r4(h), dtype=torch.float32, device=dev)
+                wh[:, :h] = first.weight.detach()[N:N + self.C[l - 1]]
+            self.Wh.append(wh)
+            self.b1.append(_bias_of(first, h, dev)), self.b2.append(_bias_of(second, C, dev))
+        # one row-padded table: a word's 2L rows are one contiguous read
+        self.t1_col, self.p_col, at = [], [], 0
+        for h, C in zip(self.h, self.C):
+            self.t1_col.append(at)
+            self.p_col.append(at + _r4(h))
+            at += _r4(h) + _r4(C)
+        tab = torch.zeros(V, at, dtype=torch.float32, device=dev)
+        for l in range(len(self.h)):
+            tab[:, self.t1_col[l]:self.t1_col[l] + self.h[l]] = xws[l]
+            tab[:, self.p_col[l]:self.p_col[l] + self.C[l]] = ps[l]
+        self._tab = tab
+        self.dis = gcn_norm_factors(g0.edge_index, g0.edge_attr, N, 1, self.degree_sum)[0][:V].clone()
+        return self
+
+    _device_csr = FoldIn._device_csr
+
+    # -- compute ----------------------------------------------------------------------------------------------------
+    def _run(self, tfidf, want_pred: bool = False, want_link: bool = False, want_hidden: bool = False, want_logits: bool = True):
+        """(logits, pred, links, hidden): lists per level (links from the second level on), None where not asked for."""
+        rowptr, col, val = self._device_csr(tfidf)
+        B, L, dev = rowptr.numel() - 1, len(self.h), self.device
+        if not _FUSED_FOLDIN:
+            return self._composed(rowptr, col, val, want_pred)
+
+        def out(width, want, dtype=torch.float32):
+            return torch.empty(B, _r4(width), dtype=dtype, device=dev) if want else None
+        logits = [out(C, want_logits) for C in self.C]
+        hidden = [out(h, want_hidden) for h in self.h]
+        links = [None] + [out(self.C[l - 1], want_link) for l in range(1, L)]
+        pred = torch.empty(L, max(B, 1), dtype=torch.int32, device=dev) if want_pred else None
+        if col.numel() == 0:                       # (data_ptr() of an empty tensor is null)
+            col = torch.zeros(1, dtype=torch.int32, device=dev)
+            val = torch.zeros(1, dtype=torch.float32, device=dev)
+
+        def ptr(t):
+            return t.data_ptr() if (t is not None and B) else None
+        lv = (_lib.FoldinLevel * L)()
+        for l in range(L):
+            lv[l] = _lib.FoldinLevel(
+                self.t1_col[l], self.p_col[l], self.W2[l].data_ptr(), self.W2[l].stride(0),
+                self.Wh[l].data_ptr() if l else None, self.Wh[l].stride(0) if l else 0, self.b1[l].data_ptr(),
+                self.b2[l].data_ptr(), ptr(logits[l]), _r4(self.C[l]), ptr(pred[l]) if want_pred else None, ptr(hidden[l]),
+                _r4(self.h[l]), ptr(links[l]), _r4(self.C[l - 1]) if l else 0, self.h[l], self.C[l], self.act[l],
+                _lib.LINKS[self.links[l - 1]] if l else 0)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().tgcn_foldin_levels(
+                B, rowptr.data_ptr(), col.data_ptr(), val.data_ptr(), self.n_vocab, self.dis.data_ptr(),
+                _lib.DEGREE_SUMS[self.degree_sum], self._tab.data_ptr(), self._tab.stride(0), L, lv, _stream_ptr(dev)))
+
+        def cut(ts, widths):
+            return [None if t is None else t[:, :w] for t, w in zip(ts, widths)]
+        return (cut(logits, self.C), None if pred is None else pred[:, :B], cut(links, [0] + self.C[:-1])[1:],
+                cut(hidden, self.h))
+
+    def _composed(self, rowptr: Tensor, col: Tensor, val: Tensor, want_pred: bool):
+        """The same definition from the package's other pieces: the document scalars as `FoldIn._composed` takes them, ONE plan
+        of the [B, V] matrix of a_j per batch (the levels share it), ONE SpMM at the combined table's width, then per level
+        `dense.xw` for H_d Wh and u W2 and torch's softmax / arg-max for the link."""
+        B, V, L, dev = rowptr.numel() - 1, self.n_vocab, len(self.h), self.device
+        reference = self.degree_sum == "reference"
+        row = torch.repeat_interleave(torch.arange(B, device=dev), rowptr[1:] - rowptr[:-1])
+        c = col.long()
+        dis_d = gcn_norm_factors(torch.stack([c, row + V]), val, V + B, 1, self.degree_sum)[0][V:]
+        dw = self.dis[c]
+        a = (dw * val) * dis_d[row] if reference else val * (dw * dis_d[row])
+        a_dd = ((dis_d * 1.0) * dis_d).unsqueeze(1)
+        if c.numel():
+            sums = GraphPlan.from_coo(row, c, a, B, V, with_transpose=False).spmm(self._tab)
+        else:
+            sums = torch.zeros(B, self._tab.size(1), dtype=torch.float32, device=dev)
+        logits, links, hidden, preds = [], [], [], []
+        for l in range(L):
+            h, C = self.h[l], self.C[l]
+            u = sums[:, self.t1_col[l]:self.t1_col[l] + h]
+            if l:
+                z_up = logits[l - 1]
+                if self.links[l - 1] == "softmax":
+                    p = torch.softmax(z_up, dim=1)
+                else:
+                    p = torch.zeros_like(z_up)
+                    if B:
+                        p[torch.arange(B, device=dev), z_up.argmax(dim=1)] = 1.0
+                links.append(p)
+                if B:
+                    u = u + a_dd * dense.xw(p.contiguous(), self.Wh[l][:, :h])
+            u = u + self.b1[l]
+            if self.act[l] == _lib.ACT_RELU:
+                u = torch.relu(u)
+            z = sums[:, self.p_col[l]:self.p_col[l] + C]
+            if B:
+                z = (z + a_dd * dense.xw(u.contiguous(), self.W2[l][:, :C])) + self.b2[l]
+            logits.append(z), hidden.append(u)
+            if want_pred:
+                preds.append(z.argmax(dim=1).to(torch.int32) if B else torch.zeros(0, dtype=torch.int32, device=dev))
+        return logits, (torch.stack(preds) if want_pred else None), links, hidden
+
+    @torch.no_grad()
+    def logits(self, tfidf) -> List[Tensor]:
+        """L tensors float32 [B, C_l]: row i of level l holds what that level's eval forward gives node N + i of
+        `extended_graph(graphs[l], tfidf, hierarchy=probabilities(tfidf)[l - 1])`."""
+        return self._run(tfidf)[0]
+
+    @torch.no_grad()
+    def predict(self, tfidf) -> Tensor:
+        """int64 [B, L]: every level's first arg-max, all from the one launch."""
+        return self._run(tfidf, want_pred=True, want_logits=False)[1].t().long()
+
+    @torch.no_grad()
+    def probabilities(self, tfidf) -> List[Tensor]:
+        """L - 1 tensors float32 [B, C_{l-1}]: the link rows -- the H a new document carries into level l = 2 .. L."""
+        return self._run(tfidf, want_link=True, want_logits=False)[2]
+
+    def predict_text(self, t2g, docs) -> Tensor:
+        """`predict(t2g.transform(docs))` for the fitted `Text2GraphTransformer` that built the graph."""
+        return self.predict(t2g.transform(docs))
+
+
+def levels_lds_bytes(h: Sequence[int], C: Sequence[int]) -> int:
+    """`tgcn_foldin_levels_lds_bytes`: the LDS a workgroup of the fused kernel needs for these widths (-1: not a shape it
+    takes).  Host arithmetic."""
+    import ctypes
+    n = len(h)
+    arr = ctypes.c_int32 * max(n, 1)
+    return int(_lib.load().tgcn_foldin_levels_lds_bytes(n, arr(*[int(v) for v in h]), arr(*[int(v) for v in C])))
