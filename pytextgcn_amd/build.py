@@ -20,6 +20,7 @@ SOURCES = ["spmm.hip", "colsum.hip", "rows.hip", "train.hip", "perlabel.hip", "c
            "graphbuilder.hip", "error.cpp"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "drop_hash.h"), os.path.join(CSRC, "fused_act.h"),
            os.path.join(CSRC, "masked_ce.h"), os.path.join(CSRC, "adam.h"), os.path.join(CSRC, "foldin.h"),
+           os.path.join(CSRC, "mlp_products.h"),
            os.path.join(_ROOT, "include", "tgcn.h")]
 
 

@@ -1,8 +1,12 @@
 // What the fold-in kernels share (foldin.hip: tgcn_foldin_two_layer; foldin_levels.hip: tgcn_foldin_levels): a document's
-// scalars, the 4-column row accesses of a lane and the u W2 epilogue.  Both kernels run THIS code, so a document's deg_d,
-// dis_d, a_j, a_dd and its level-1 sums carry the same bits in either.
+// scalars, the 4-column row accesses of a lane, the wave-local LDS sync, the u W2 epilogue and the launch (launch_fold).
+// Both kernels run THIS code, so a document's deg_d, dis_d, a_j, a_dd and its level-1 sums carry the same bits in either.
+// The pass over a document's words is NOT here: each kernel spells its own out (one body for both measured slower in
+// either kernel).
 #pragma once
 
+#include <algorithm>
+#include <atomic>
 #include <climits>
 
 #include "common.h"
@@ -110,6 +114,14 @@ __device__ __forceinline__ void doc_entry(const int32_t *__restrict__ col, const
     }
 }
 
+// A wave's LDS slice belongs to that wave alone: its LDS operations run in order, so a wave-local fence and barrier stand
+// between the slice's stores and the loads that follow them
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // y = u W2 for the columns `lane` (y0) and, WIDE, `lane + 64` (y1): u [h] in the wave's LDS slice, w0 / w1 point at the
 // lane's column of the tight [h, C] copy of W2 in LDS; k = 0 .. h-1 in order, one FMA per term
 template <bool WIDE>
@@ -159,6 +171,26 @@ __device__ __forceinline__ int first_argmax(const float z0, const float z1, cons
 }
 
 inline bool aligned16(const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+
+// The launch of a fold-in leaf `Kernel` (one wave per document, grid-stride, at most TGCN_FOLDIN_WORKGROUP_CAP workgroups)
+// with `lds_bytes` of dynamic LDS.  The leaf's LDS ceiling is raised to `lds_ceiling` once per device, not per launch: the
+// call is host work on a path whose cost is the host's (a device ordinal beyond the table asks every time).
+template <auto Kernel, class Args>
+int launch_fold(const Args &A, int64_t n_docs, int lds_ceiling, size_t lds_bytes, hipStream_t s) {
+    static std::atomic<bool> raised[64] = {};            // (one table per kernel symbol)
+    int dev = -1;
+    const bool known = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64;
+    if (!known || !raised[dev].load(std::memory_order_acquire)) {
+        TGCN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           lds_ceiling));
+        if (known) raised[dev].store(true, std::memory_order_release);
+    }
+    const int grid =
+        static_cast<int>(std::min<int64_t>((n_docs + kFoldWaves - 1) / kFoldWaves, int64_t(TGCN_FOLDIN_WORKGROUP_CAP)));
+    hipLaunchKernelGGL(Kernel, dim3(grid), dim3(64 * kFoldWaves), lds_bytes, s, A);
+    TGCN_HIP_CHECK(hipGetLastError());
+    return TGCN_OK;
+}
 
 }  // namespace fold
 }  // namespace tgcn

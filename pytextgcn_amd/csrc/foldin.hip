@@ -10,12 +10,10 @@
 //   3. u = act(. + a_dd s1 + b1) goes to the wave's LDS slice (and to `hidden`), the gathered P sum next to it; then
 //      u W2 from the workgroup's LDS copy of W2: lane l owns the columns l and l + 64, k in order; z, the store, arg-max.
 // A document's arithmetic is a function of (h, C) and its own row: the leaf never depends on the batch or the row length.
-// The document scalars, the row accesses and the u W2 epilogue live in foldin.h: foldin_levels.hip runs the same code.
+// The document scalars, the row accesses, the wave-local LDS sync, the u W2 epilogue and the launch live in foldin.h:
+// foldin_levels.hip runs the same code.  The pass over the words is written out in both kernels.
 // Leaves (template): TAIL = h or C is not a multiple of 4 (the last lane of a row loads and stores scalars),
 //                    WIDE = C > 64 (a second column per lane in the epilogue).
-#include <algorithm>
-#include <atomic>
-
 #include "foldin.h"
 
 namespace tgcn {
@@ -125,9 +123,7 @@ __global__ __launch_bounds__(64 * kFoldWaves) void k_foldin(const FoldArgs A) {
         if (c0 < H4) *reinterpret_cast<float4 *>(us + c0) = u;
         if (c0 < C4) *reinterpret_cast<float4 *>(zs + c0) = accP;
         if (A.hidden) store4<TAIL>(A.hidden + d * A.ldh, c0, h, u);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();                 // the slice belongs to this wave: its LDS operations run in order
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
 
         float y0, y1;
         u_times_w2<WIDE>(us, w0, w1, h, C, y0, y1);
@@ -158,23 +154,9 @@ size_t foldin_lds_bytes(int h, int C) {
 
 template <bool TAIL, bool WIDE>
 int launch_foldin(const FoldArgs &A, hipStream_t s) {
-    const size_t lds_bytes = foldin_lds_bytes(A.h, A.C);
-    // the leaf's LDS ceiling is raised to the largest shape once per device, not per launch: the call is host work on a
-    // path whose cost is the host's (a device ordinal beyond the table asks every time)
-    static std::atomic<bool> raised[64] = {};
-    int dev = -1;
-    const bool known = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64;
-    if (!known || !raised[dev].load(std::memory_order_acquire)) {
-        const void *fn = reinterpret_cast<const void *>(&k_foldin<TAIL, WIDE>);
-        TGCN_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           static_cast<int>(foldin_lds_bytes(kFoldMaxH, kFoldMaxC))));
-        if (known) raised[dev].store(true, std::memory_order_release);
-    }
-    const int grid = static_cast<int>(
-        std::min<int64_t>((A.n_docs + kFoldWaves - 1) / kFoldWaves, int64_t(TGCN_FOLDIN_WORKGROUP_CAP)));
-    k_foldin<TAIL, WIDE><<<grid, 64 * kFoldWaves, lds_bytes, s>>>(A);
-    TGCN_HIP_CHECK(hipGetLastError());
-    return TGCN_OK;
+    // the leaf's LDS ceiling is that of the largest shape
+    return launch_fold<k_foldin<TAIL, WIDE>>(A, A.n_docs, static_cast<int>(foldin_lds_bytes(kFoldMaxH, kFoldMaxC)),
+                                             foldin_lds_bytes(A.h, A.C), s);
 }
 
 }  // namespace

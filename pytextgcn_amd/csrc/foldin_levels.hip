@@ -3,7 +3,10 @@
 // The reference runs the strategy on graph nodes only (perlevel_amazon.py, perlevel_dbpedia.py).
 //
 // One wavefront per document, kFoldWaves documents per workgroup pass, grid-stride over the batch, as foldin.hip -- and the
-// document's scalars, row accesses and u W2 epilogue ARE foldin.hip's (foldin.h).  Per document:
+// document's scalars, row accesses, wave-local LDS sync, u W2 epilogue and the launch ARE foldin.hip's (foldin.h).  The pass
+// over the words is written out here as it is there: one body for both (2 segments of two tables, 2L segments of one) gave
+// the same bits but measured slower in leaves of either kernel (profiles/r21_shared_bodies_isa.md).
+// Per document:
 //   1. deg_d, dis_d, a_dd once.
 //   2. ONE pass over the words: column id and a_j through v_readlane, then the word's row of the combined table, which
 //      holds the 2L segments T1^l[w], P^l[w] (one scalar row address, one loop-invariant lane offset per segment); lane i
@@ -17,9 +20,6 @@
 //      u^l -> slice; u^l W2^l from the LDS copy of W2^l; z^l; arg-max; the next level's link.
 // Leaves (template): L in {2, 3}; TAIL = some h_l or C_l is not a multiple of 4; WIDE = some C_l > 64.  act and link are
 // per level and read at run time.  A document's arithmetic is a function of the widths and its own row.
-#include <algorithm>
-#include <atomic>
-
 #include "foldin.h"
 
 namespace tgcn {
@@ -53,12 +53,6 @@ struct LevelsArgs {
     int slice_off, slice;            // floats: the first wave's slice, and a slice's size
     LevelK lv[kMaxLevels];
 };
-
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();                     // the slice belongs to this wave: its LDS operations run in order
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 template <int L, bool TAIL, bool WIDE>
 __global__ __launch_bounds__(64 * kFoldWaves) void k_foldin_levels(const LevelsArgs A) {
@@ -277,20 +271,7 @@ bool widths_ok(int L, const int32_t *h, const int32_t *C) {
 
 template <int L, bool TAIL, bool WIDE>
 int launch_levels(const LevelsArgs &A, size_t lds_bytes, hipStream_t s) {
-    // the leaf's LDS ceiling is raised to the limit once per device, not per launch (as foldin.hip does)
-    static std::atomic<bool> raised[64] = {};
-    int dev = -1;
-    const bool known = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64;
-    if (!known || !raised[dev].load(std::memory_order_acquire)) {
-        const void *fn = reinterpret_cast<const void *>(&k_foldin_levels<L, TAIL, WIDE>);
-        TGCN_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, TGCN_FOLDIN_LEVELS_LDS_LIMIT));
-        if (known) raised[dev].store(true, std::memory_order_release);
-    }
-    const int grid = static_cast<int>(
-        std::min<int64_t>((A.n_docs + kFoldWaves - 1) / kFoldWaves, int64_t(TGCN_FOLDIN_WORKGROUP_CAP)));
-    k_foldin_levels<L, TAIL, WIDE><<<grid, 64 * kFoldWaves, lds_bytes, s>>>(A);
-    TGCN_HIP_CHECK(hipGetLastError());
-    return TGCN_OK;
+    return launch_fold<k_foldin_levels<L, TAIL, WIDE>>(A, A.n_docs, TGCN_FOLDIN_LEVELS_LDS_LIMIT, lds_bytes, s);
 }
 
 template <int L>

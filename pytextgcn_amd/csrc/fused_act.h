@@ -1,6 +1,7 @@
-// What the fused-activation products (embed.hip, mlp.hip) and the other matrix-core kernels of the model layers (jk.hip,
-// hier.hip's entry points) share: the accumulator map of v_mfma_f32_32x32x2_f32, SELU, the dropout decision of one
-// element, the argument checks of the entry points, the cut of a reduction into slices and the sum over the slices.
+// What the fused-activation products (embed.hip; mlp.hip and mlp_grouped.hip through mlp_products.h) and the other
+// matrix-core kernels of the model layers (jk.hip, hier.hip's entry points) share: the accumulator map of
+// v_mfma_f32_32x32x2_f32, SELU, the dropout decision of one element, the argument checks of the entry points, the cut of a
+// reduction into slices and the sum over the slices (reduce_slices: the body of k_reduce_slices and of k_gmlp_reduce_w).
 // Everything here is inline, a template or in an unnamed namespace: a translation unit holds a copy of what it uses.
 #pragma once
 

@@ -9,18 +9,19 @@
 //                                        dc[col0_g + m] = sum over the rows i of group g of G[i, col0_g + m]
 // keep(i, j) is the hash of drop_hash.h for mask row mask_row0 + i (i the row's index in grouped order) and column j.
 //
-// The kernels are those of mlp.hip with one indirection: a workgroup does not own rows 128 blockIdx.x ... but one TILE of
-// a table built on the host (tgcn_mlp_grouped_layout): at most 128 rows that all belong to one group, so the W / b tiles
-// it stages in LDS are that group's, and the rows past the tile's count are masked as mlp.hip masks the rows past N.  The
-// sums of an element run over k (forward) and over m (dZ) exactly as in k_mlp_fwd / k_mlp_grad_z, whatever the row
-// tiling: group g's slice of C and dZ has the bits of tgcn_mlp_act_linear* on Z[row_ptr[g] : row_ptr[g + 1]] with
-// mask_row0 + row_ptr[g].  dW is cut into slices of whole chunks of kWChunk rows inside one group and reduced per group
-// in slice order, db is a column sum per tile reduced per group in tile order: no atomics, the host never loops over the
-// groups, and the launch count depends on n and k only.
+// The kernels run the bodies of mlp.hip's (mlp_products.h: mlp_fwd and mlp_grad_z with CLS = false, mlp_grad_w) with one
+// indirection: a workgroup does not own rows 128 blockIdx.x ... but one TILE of a table built on the host
+// (tgcn_mlp_grouped_layout): at most 128 rows that all belong to one group, so the W / b tiles it stages in LDS are that
+// group's, and the rows past the tile's count are masked as the rows past N are.  A kernel here reads its tile or slice
+// and its group, moves W, b, G, C and c to the group's and calls the body.  The sums of an element run over k (forward)
+// and over m (dZ) in the one body, whatever the row tiling: group g's slice of C and dZ has the bits of
+// tgcn_mlp_act_linear* on Z[row_ptr[g] : row_ptr[g + 1]] with mask_row0 + row_ptr[g].  dW is cut into slices of whole
+// chunks of kWChunk rows inside one group and reduced per group in slice order, db is a column sum per tile reduced per
+// group in tile order: no atomics, the host never loops over the groups, and the launch count depends on n and k only.
 #include <algorithm>
 #include <cstring>
 
-#include "fused_act.h"
+#include "mlp_products.h"
 
 namespace tgcn {
 namespace {
@@ -62,79 +63,26 @@ inline GTables tables_of(const void *blob, const GHeader &h) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Forward: k_mlp_fwd (mlp.hip) on one tile of the table.  `cg0`: the first result column of this launch inside every
-// group's n_g columns (groups of kFwdGroup); a group that is narrower than cg0 has nothing here.
+// Forward: mlp_fwd on one tile of the table.  `cg0`: the first result column of this launch inside every group's n_g
+// columns (groups of kFwdGroup); a group that is narrower than cg0 has nothing here.
 // ---------------------------------------------------------------------------------------------
 template <int NT, bool DROP>
 __global__ __launch_bounds__(256, 2) void k_gmlp_fwd(const GTile *__restrict__ tiles, const GGroup *__restrict__ groups,
                                                      const float *__restrict__ Z, int64_t ldz, const float *__restrict__ b,
                                                      const float *__restrict__ W, int64_t ldw, const float *__restrict__ cb,
                                                      float *__restrict__ C, int64_t ldc, int K, int cg0, const RowDrop d) {
-    constexpr int KC = 32, NP = 32 * NT, LD = KC + 1;
-    __shared__ float Ws[NP * LD];
-    __shared__ float Zs[128 * LD];
-    __shared__ float bs[KC];
     const GTile tile = tiles[blockIdx.x];
     const GGroup grp = groups[tile.group];
     const int n = min(grp.n - cg0, kFwdGroup);
     if (n <= 0) return;                                    // (the whole workgroup: no barrier has been reached)
-    W += int64_t(grp.w_row0 + cg0) * ldw;
-    b += grp.b_off;
-    C += grp.col0 + cg0;
-    if (cb != nullptr) cb += grp.col0 + cg0;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, c = lane & 31;
-    const int64_t blk0 = tile.row0, N = tile.row0 + tile.count;
-    const int64_t row0 = blk0 + wave * 32;
-    const int64_t i = row0 + c;
-    const bool live = i < N;
-    const uint32_t key = row_key<DROP>(d, i);
-    const int skk = tid & 31, sr = tid >> 5;
-    f32x16 acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-
-    for (int k0 = 0; k0 < K; k0 += KC) {
-        const bool kin = k0 + skk < K;
-        __syncthreads();                                   // the previous chunk has been read
-#pragma unroll 4
-        for (int u = 0; u < 4 * NT; ++u) {
-            const int m = sr + 8 * u;
-            Ws[m * LD + skk] = (kin && m < n) ? W[int64_t(m) * ldw + k0 + skk] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            const int r = sr + 8 * u;
-            Zs[r * LD + skk] = (kin && blk0 + r < N) ? Z[(blk0 + r) * ldz + k0 + skk] : 0.f;
-        }
-        if (tid < KC) bs[tid] = kin ? b[k0 + tid] : 0.f;
-        __syncthreads();
-        const float *zr = Zs + (wave * 32 + c) * LD;
-#pragma unroll
-        for (int s = 0; s < KC / 2; ++s) {
-            const int kk = 2 * s + half, k = k0 + kk;
-            const float a = (live && k < K) ? act<DROP>(zr[kk] + bs[kk], key, drop_col_term(k), d) : 0.f;
-#pragma unroll
-            for (int t = 0; t < NT; ++t)
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, Ws[(32 * t + c) * LD + kk], acc[t], 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int col = 32 * t + c;
-        const float bias = (cb != nullptr && col < n) ? cb[col] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int64_t row = row0 + acc_row(r, half);
-            if (row < N && col < n) C[row * ldc + col] = acc[t][r] + bias;
-        }
-    }
+    mlp_fwd<NT, DROP, false>(Z, ldz, b + grp.b_off, W + int64_t(grp.w_row0 + cg0) * ldw, ldw,
+                             cb != nullptr ? cb + grp.col0 + cg0 : nullptr, C + grp.col0 + cg0, ldc, tile.row0,
+                             tile.row0 + tile.count, K, n, d, ClassTerm{});
 }
 
 // ---------------------------------------------------------------------------------------------
-// dZ: k_mlp_grad_z (mlp.hip) on one tile of the table.  `mg0`: the first index m of this launch's piece of the reduction
-// (pieces of kGzGroup; `accum` on every piece but the first, as in mlp.hip); a group with n_g <= mg0 adds nothing.
+// dZ: mlp_grad_z on one tile of the table.  `mg0`: the first index m of this launch's piece of the reduction (pieces of
+// kGzGroup; `accum` on every piece but the first, as in mlp.hip); a group with n_g <= mg0 adds nothing.
 // ---------------------------------------------------------------------------------------------
 template <int NT, bool DROP>
 __global__ __launch_bounds__(256, 2) void k_gmlp_grad_z(const GTile *__restrict__ tiles, const GGroup *__restrict__ groups,
@@ -142,168 +90,41 @@ __global__ __launch_bounds__(256, 2) void k_gmlp_grad_z(const GTile *__restrict_
                                                         const float *__restrict__ W, int64_t ldw,
                                                         const float *__restrict__ G, int64_t ldg, float *__restrict__ dZ,
                                                         int64_t lddz, int K, int mg0, const RowDrop d) {
-    constexpr int NP = 32 * NT;
-    __shared__ float Ws[NP * 32];
-    __shared__ float Gs[4 * 32 * 33];
-    __shared__ float bs[32];
     const GTile tile = tiles[blockIdx.x];
     const GGroup grp = groups[tile.group];
     const int n = min(grp.n - mg0, kGzGroup);
     if (n <= 0) return;                                    // (mg0 > 0: what dZ holds is already the whole sum)
-    const int accum = mg0 > 0;
-    W += int64_t(grp.w_row0 + mg0) * ldw;
-    b += grp.b_off;
-    G += grp.col0 + mg0;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, c = lane & 31;
-    const int64_t N = tile.row0 + tile.count;
-    const int64_t row0 = tile.row0 + wave * 32;
-    const int sj = tid & 31, sr = tid >> 5;
-    float *gw = Gs + wave * (32 * 33);                     // this wave's 32 x 32 tile of G, [row][33]
-    float g[16 * NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int m = 32 * t + c;
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {                     // lanes along a row of G: 128 bytes per half wave
-            const int r = 2 * u + half;
-            gw[r * 33 + c] = (row0 + r < N && m < n) ? G[(row0 + r) * ldg + m] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < 16; ++s) g[16 * t + s] = gw[c * 33 + 2 * s + half];   // lane c takes row c, column 2 s + half
-        __syncthreads();
-    }
-    uint32_t keys[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) keys[r] = row_key<DROP>(d, row0 + acc_row(r, half));
-
-    for (int j0 = 0; j0 < K; j0 += 32) {
-        __syncthreads();                                   // the previous tile has been read
-#pragma unroll 4
-        for (int u = 0; u < 4 * NT; ++u) {
-            const int m = sr + 8 * u;
-            Ws[m * 32 + sj] = (j0 + sj < K && m < n) ? W[int64_t(m) * ldw + j0 + sj] : 0.f;
-        }
-        if (tid < 32) bs[tid] = j0 + tid < K ? b[j0 + tid] : 0.f;
-        const int j = j0 + c;
-        float z[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int64_t row = row0 + acc_row(r, half);
-            z[r] = (row < N && j < K) ? Z[row * ldz + j] : 0.f;
-        }
-        __syncthreads();
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-        for (int s = 0; s < 16 * NT; ++s)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(g[s], Ws[(2 * s + half) * 32 + c], acc, 0, 0, 0);
-        const float bj = bs[c];
-        const uint32_t col_term = drop_col_term(j);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int64_t row = row0 + acc_row(r, half);
-            if (row < N && j < K) {
-                float v = acc[r] * selu_grad_f(z[r] + bj);
-                if constexpr (DROP) v = drop_hash_keep(keys[r], col_term, d.thresh) ? v * d.scale : 0.f;
-                float *out = dZ + row * lddz + j;
-                *out = accum ? *out + v : v;
-            }
-        }
-    }
+    mlp_grad_z<NT, DROP, false>(Z, ldz, b + grp.b_off, W + int64_t(grp.w_row0 + mg0) * ldw, ldw, G + grp.col0 + mg0, ldg, dZ,
+                                lddz, tile.row0, tile.row0 + tile.count, K, n, mg0 > 0, d, ClassTerm{});
 }
 
 // ---------------------------------------------------------------------------------------------
-// dW: k_mlp_grad_w (mlp.hip) on one slice of the table (blockIdx.y): whole chunks of kWChunk rows of ONE group, so the
-// bias and the columns of G are that group's.  `m0`: the first row of dW of this launch inside every group's n_g rows
-// (groups of kWGroup).  The partial sums of slice q lie at part[q], as in mlp.hip; k_gmlp_reduce_w adds a group's slices.
+// dW: mlp_grad_w on one slice of the table (blockIdx.y): whole chunks of kWChunk rows of ONE group, so the bias and the
+// columns of G are that group's.  `m0`: the first row of dW of this launch inside every group's n_g rows (groups of
+// kWGroup).  The partial sums of slice q lie at part[q], as in mlp.hip; k_gmlp_reduce_w adds a group's slices.
 // ---------------------------------------------------------------------------------------------
 template <int TW, bool DROP>
 __global__ __launch_bounds__(256, 2) void k_gmlp_grad_w(const GSlice *__restrict__ slices, const GGroup *__restrict__ groups,
                                                         const float *__restrict__ Z, int64_t ldz, const float *__restrict__ b,
                                                         const float *__restrict__ G, int64_t ldg, float *__restrict__ part,
                                                         int K, int m0, const RowDrop d) {
-    constexpr int NP = 128 * TW;
-    __shared__ float As[kWChunk * 32];
-    __shared__ uint32_t ks[kWChunk];
     const GSlice slice = slices[blockIdx.y];
     const GGroup grp = groups[slice.group];
     const int n = min(grp.n - m0, kWGroup);
     if (n <= 0) return;                                    // (k_gmlp_reduce_w reads no row of this group in this launch)
-    b += grp.b_off;
-    G += grp.col0 + m0;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, c = lane & 31;
-    const int j0 = blockIdx.x * 32;
-    const int kpad = gridDim.x * 32;
-    const int64_t i_begin = slice.row0, i_end = slice.row_end;
-    const bool computes = wave * TW * 32 < n;             // a wave whose rows of dW are all padding only helps staging
-    const int sj = tid & 31, sr = tid >> 5;
-    const int j = j0 + sj;
-    const float bj = j < K ? b[j] : 0.f;
-    const uint32_t col_term = drop_col_term(j);
-    f32x16 acc[TW];
-#pragma unroll
-    for (int t = 0; t < TW; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-
-    for (int64_t i0 = i_begin; i0 < i_end; i0 += kWChunk) {
-        float z[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            const int64_t i = i0 + sr + 8 * u;
-            z[u] = (i < i_end && j < K) ? Z[i * ldz + j] : 0.f;
-        }
-        __syncthreads();                                   // the previous tile has been read
-        if constexpr (DROP) {
-            if (tid < kWChunk) ks[tid] = row_key<DROP>(d, i0 + tid);
-            __syncthreads();
-        }
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            const int r = sr + 8 * u;
-            const int64_t i = i0 + r;
-            const uint32_t key = DROP ? ks[r] : 0u;
-            As[r * 32 + sj] = (i < i_end && j < K) ? act<DROP>(z[u] + bj, key, col_term, d) : 0.f;
-        }
-        __syncthreads();
-        if (computes) {
-#pragma unroll 8
-            for (int s = 0; s < kWChunk / 2; ++s) {
-                const int ii = 2 * s + half;
-                const int64_t i = i0 + ii;
-                const float a = As[ii * 32 + c];
-#pragma unroll
-                for (int t = 0; t < TW; ++t) {
-                    const int m = (wave * TW + t) * 32 + c;
-                    const float gv = (i < i_end && m < n) ? G[i * ldg + m] : 0.f;
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(gv, a, acc[t], 0, 0, 0);
-                }
-            }
-        }
-    }
-    float *out = part + int64_t(blockIdx.y) * NP * kpad + j0 + c;
-#pragma unroll
-    for (int t = 0; t < TW; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) out[int64_t((wave * TW + t) * 32 + acc_row(r, half)) * kpad] = acc[t][r];
+    mlp_grad_w<TW, DROP>(Z, ldz, b + grp.b_off, G + grp.col0 + m0, ldg, part, slice.row0, slice.row_end, K, n, d);
 }
 
-// dW[w_row0_g + m0 + r, j] = the sum over the slices of group g (blockIdx.y), in order, of their partial sums: k_reduce_slices
-// with the slice range taken from the table.  A group without rows has no slice: exact zeros.
+// dW[w_row0_g + m0 + r, j] = the sum over the slices of group g (blockIdx.y), in order, of their partial sums: reduce_slices
+// (fused_act.h) on the slice range taken from the table.  A group without rows has no slice: exact zeros.
 __global__ __launch_bounds__(256) void k_gmlp_reduce_w(const float *__restrict__ part, const GGroup *__restrict__ groups,
                                                        int64_t slice_stride, int row_stride, int cols, int m0,
                                                        float *__restrict__ dW, int64_t lddw) {
     const GGroup grp = groups[blockIdx.y];
     const int rows = min(grp.n - m0, kWGroup);
-    const int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x;
-    if (rows <= 0 || e >= int64_t(rows) * cols) return;
-    const int r = static_cast<int>(e / cols), j = static_cast<int>(e % cols);
-    const float *p = part + int64_t(grp.slice0) * slice_stride + int64_t(r) * row_stride + j;
-    float s = 0.f;
-    for (int q = 0; q < grp.n_slices; ++q) s += p[q * slice_stride];
-    dW[int64_t(grp.w_row0 + m0 + r) * lddw + j] = s;
+    if (rows <= 0) return;
+    reduce_slices(part + int64_t(grp.slice0) * slice_stride, grp.n_slices, slice_stride, row_stride, rows, cols,
+                  dW + int64_t(grp.w_row0 + m0) * lddw, lddw);
 }
 
 // db, first pass: the column sums of dZ over one tile (blockIdx.x) for 32 columns (blockIdx.y).  Thread (sr, c) adds rows

@@ -108,6 +108,50 @@ def extended_graph(g, tfidf, hierarchy=None) -> Data:
     return out
 
 
+def _r4(v: int) -> int:
+    return (v + 3) & ~3
+
+
+def _bias_of(layer, n: int, dev) -> Tensor:
+    return torch.zeros(n, dtype=torch.float32, device=dev) if layer.bias is None else layer.bias.detach().float().clone()
+
+
+def _check_two_layer(who: str, convs, activation, at: str = "", layers_note: str = "") -> Tuple[int, int]:
+    """What both fold-in kernels ask of a network: two GCNConv layers with self loops and normalisation, ReLU or nothing
+    (`activation`: the module between the layers, None where there is none).  `at` names the level in the error texts.
+    Returns the widths (h, C), which `_check_widths` holds against the kernels'."""
+    if len(convs) != 2:
+        raise NotImplementedError(f"{who}:{at} n_gcn != 2 (the model has {len(convs)} GCNConv layers){layers_note}")
+    for c in convs:
+        if not (c.add_self_loops and c.normalize) or c.improved:
+            raise NotImplementedError(f"{who}: GCNConv(add_self_loops=True, normalize=True, improved=False) only")
+    if activation is not None and type(activation) is not nn.ReLU:
+        raise NotImplementedError(f"{who}:{at} other activations than nn.ReLU are not supported "
+                                  f"({type(activation).__name__})")
+    return convs[0].out_channels, convs[1].out_channels
+
+
+def _check_widths(who: str, h: int, C: int, at: str = "") -> None:
+    lib = _lib.load()
+    if h > lib.tgcn_foldin_max_hidden() or C > lib.tgcn_foldin_max_classes():
+        raise NotImplementedError(f"{who}:{at} hidden width {h} / {C} classes exceed the kernel's "
+                                  f"{lib.tgcn_foldin_max_hidden()} / {lib.tgcn_foldin_max_classes()}")
+
+
+def _doc_scalars(rowptr: Tensor, col: Tensor, val: Tensor, dis: Tensor, V: int, degree_sum: str):
+    """What both `_composed` methods begin with: a_dd [B, 1] and the plan of the [B, V] matrix of a_j (None for a batch
+    without entries).  deg_d comes from `tgcn_gcn_norm` on the bipartite word -> document edges (the plan's own sums, in
+    edge = CSR order, the loop last).  Builds a plan per batch, which sorts and synchronises."""
+    B, dev = rowptr.numel() - 1, rowptr.device
+    row = torch.repeat_interleave(torch.arange(B, device=dev), rowptr[1:] - rowptr[:-1])
+    c = col.long()
+    dis_d = gcn_norm_factors(torch.stack([c, row + V]), val, V + B, 1, degree_sum)[0][V:]
+    dw = dis[c]
+    a = (dw * val) * dis_d[row] if degree_sum == "reference" else val * (dw * dis_d[row])
+    a_dd = ((dis_d * 1.0) * dis_d).unsqueeze(1)
+    return a_dd, (GraphPlan.from_coo(row, c, a, B, V, with_transpose=False) if c.numel() else None)
+
+
 class FoldIn:
     """`FoldIn(model, g)`: classify documents outside the training graph `g` with the trained `model` -- `models.GCN` (linear,
     or `apply_activation=True` with `nn.ReLU`) or `models.EGCN`, two GCNConv layers, sparse identity features.  The tables
@@ -135,15 +179,8 @@ class FoldIn:
             why = next((text for classes, text in causes if isinstance(model, classes)), "unsupported model type")
             raise NotImplementedError(f"FoldIn takes models.GCN and models.EGCN, not {kind.__name__} ({why})")
         convs = list(model.layers)[(1 if kind is M.EGCN else 0):]
-        if len(convs) != 2:
-            raise NotImplementedError(f"FoldIn: n_gcn != 2 (the model has {len(convs)} GCNConv layers); the closed form is "
-                                      "the two-layer network's")
-        for c in convs:
-            if not (c.add_self_loops and c.normalize) or c.improved:
-                raise NotImplementedError("FoldIn: GCNConv(add_self_loops=True, normalize=True, improved=False) only")
-        if kind is M.GCN and getattr(model, "apply_activation", False) and type(model.activation) is not nn.ReLU:
-            raise NotImplementedError(f"FoldIn: other activations than nn.ReLU are not supported "
-                                      f"({type(model.activation).__name__})")
+        between = model.activation if (kind is M.GCN and getattr(model, "apply_activation", False)) else None
+        h, C = _check_two_layer("FoldIn", convs, between, layers_note="; the closed form is the two-layer network's")
         x = g.x
         if isinstance(x, hier.HierarchyFeatures):
             raise NotImplementedError("FoldIn: [I | H] hierarchy features (HierarchyFeatures) are not supported")
@@ -154,11 +191,7 @@ class FoldIn:
                 raise NotImplementedError("FoldIn: [I | H] hierarchy features are not supported")
             raise NotImplementedError("FoldIn: non-identity features are not supported (sparse identity features only)")
         _require_cuda(x, "g.x")
-        lib = _lib.load()
-        h, C = convs[0].out_channels, convs[1].out_channels
-        if h > lib.tgcn_foldin_max_hidden() or C > lib.tgcn_foldin_max_classes():
-            raise NotImplementedError(f"FoldIn: hidden width {h} / {C} classes exceed the kernel's "
-                                      f"{lib.tgcn_foldin_max_hidden()} / {lib.tgcn_foldin_max_classes()}")
+        _check_widths("FoldIn", h, C)
 
     # -- the frozen tables ------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -195,7 +228,7 @@ class FoldIn:
         finally:
             model.train(was_training)
         h, C = self.h, self.C
-        H4, C4 = (h + 3) & ~3, (C + 3) & ~3
+        H4, C4 = _r4(h), _r4(C)
         # one row-padded table: a word's T1 row and P row are one contiguous read
         tab = torch.zeros(V, H4 + C4, dtype=torch.float32, device=dev)
         tab[:, :h] = xw.detach()[:V]
@@ -204,10 +237,7 @@ class FoldIn:
         self.W2 = torch.zeros(h, C4, dtype=torch.float32, device=dev)
         self.W2[:, :C] = second.weight.detach()
         self.s1 = None if s1 is None else s1.detach().float().clone()
-
-        def bias_of(layer, n):
-            return torch.zeros(n, dtype=torch.float32, device=dev) if layer.bias is None else layer.bias.detach().float().clone()
-        self.b1, self.b2 = bias_of(first, h), bias_of(second, C)
+        self.b1, self.b2 = _bias_of(first, h, dev), _bias_of(second, C, dev)
         self.dis = gcn_norm_factors(g.edge_index, g.edge_attr, N, 1, self.degree_sum)[0][:V].clone()
         return self
 
@@ -232,7 +262,7 @@ class FoldIn:
         if not _FUSED_FOLDIN:
             return self._composed(rowptr, col, val, want_pred, want_hidden)
         h, C = self.h, self.C
-        H4, C4 = (h + 3) & ~3, (C + 3) & ~3
+        H4, C4 = _r4(h), _r4(C)
         dev = self.device
         logits = torch.empty(B, C4, dtype=torch.float32, device=dev)
         pred = torch.empty(B, dtype=torch.int32, device=dev) if want_pred else None
@@ -251,19 +281,11 @@ class FoldIn:
         return logits[:, :C], pred, (hidden[:, :h] if want_hidden else None)
 
     def _composed(self, rowptr: Tensor, col: Tensor, val: Tensor, want_pred: bool, want_hidden: bool):
-        """The same definition from the package's other pieces: `tgcn_gcn_norm` on the bipartite word -> document edges for
-        deg_d (the plan's own sums, in edge = CSR order, the loop last), a plan of the [B, V] matrix of a_j, two SpMMs, one
-        dense product and a row scale.  Builds a plan per batch, which sorts and synchronises."""
-        B, V, dev = rowptr.numel() - 1, self.n_vocab, self.device
-        reference = self.degree_sum == "reference"
-        row = torch.repeat_interleave(torch.arange(B, device=dev), rowptr[1:] - rowptr[:-1])
-        c = col.long()
-        dis_d = gcn_norm_factors(torch.stack([c, row + V]), val, V + B, 1, self.degree_sum)[0][V:]
-        dw = self.dis[c]
-        a = (dw * val) * dis_d[row] if reference else val * (dw * dis_d[row])
-        a_dd = ((dis_d * 1.0) * dis_d).unsqueeze(1)
-        if c.numel():
-            op = GraphPlan.from_coo(row, c, a, B, V, with_transpose=False)
+        """The same definition from the package's other pieces: the document scalars and a plan of the [B, V] matrix of a_j
+        (`_doc_scalars`: a plan per batch), two SpMMs, one dense product and a row scale."""
+        B, dev = rowptr.numel() - 1, self.device
+        a_dd, op = _doc_scalars(rowptr, col, val, self.dis, self.n_vocab, self.degree_sum)
+        if op is not None:
             u, zg = op.spmm(self.T1), op.spmm(self.P)
         else:
             u = torch.zeros(B, self.h, dtype=torch.float32, device=dev)
@@ -295,14 +317,6 @@ class FoldIn:
         return self.predict(t2g.transform(docs))
 
 
-def _bias_of(layer, n: int, dev) -> Tensor:
-    return torch.zeros(n, dtype=torch.float32, device=dev) if layer.bias is None else layer.bias.detach().float().clone()
-
-
-def _r4(v: int) -> int:
-    return (v + 3) & ~3
-
-
 class FoldInLevels:
     """`FoldInLevels(models, graphs, link="softmax")`: classify documents outside the training graph through the per-level
     strategy.  `models` are the L = 2 or 3 trained two-layer `models.GCN` (linear, or `apply_activation=True` with `nn.ReLU`),
@@ -324,7 +338,6 @@ class FoldInLevels:
     @staticmethod
     def _check(models, graphs, links) -> None:
         from . import models as M
-        lib = _lib.load()
         L = len(models)
         if not 2 <= L <= _lib.FOLDIN_MAX_LEVELS or len(graphs) != L:
             raise ValueError(f"FoldInLevels: 2 or {_lib.FOLDIN_MAX_LEVELS} levels, one graph per model ({L} models, "
@@ -340,14 +353,8 @@ class FoldInLevels:
                 raise NotImplementedError(f"FoldInLevels: level {l + 1} is a {type(model).__name__}, every level must be a "
                                           f"two-layer models.GCN ({why})")
             convs = list(model.layers)
-            if len(convs) != 2:
-                raise NotImplementedError(f"FoldInLevels: level {l + 1}: n_gcn != 2 (the model has {len(convs)} GCNConv layers)")
-            for c in convs:
-                if not (c.add_self_loops and c.normalize) or c.improved:
-                    raise NotImplementedError("FoldInLevels: GCNConv(add_self_loops=True, normalize=True, improved=False) only")
-            if getattr(model, "apply_activation", False) and type(model.activation) is not nn.ReLU:
-                raise NotImplementedError(f"FoldInLevels: level {l + 1}: other activations than nn.ReLU are not supported "
-                                          f"({type(model.activation).__name__})")
+            between = model.activation if getattr(model, "apply_activation", False) else None
+            h, C = _check_two_layer("FoldInLevels", convs, between, at=f" level {l + 1}:")
             if l > 0:
                 for name in ("edge_index", "edge_attr"):
                     a, b = getattr(g0, name), getattr(g, name)
@@ -375,11 +382,9 @@ class FoldInLevels:
             if convs[0].in_channels != x.size(1):
                 raise ValueError(f"FoldInLevels: level {l + 1}'s model takes {convs[0].in_channels} features, its graph has "
                                  f"{x.size(1)}")
-            hs.append(convs[0].out_channels)
-            Cs.append(convs[1].out_channels)
-            if hs[l] > lib.tgcn_foldin_max_hidden() or Cs[l] > lib.tgcn_foldin_max_classes():
-                raise NotImplementedError(f"FoldInLevels: level {l + 1}: hidden width {hs[l]} / {Cs[l]} classes exceed the "
-                                          f"kernel's {lib.tgcn_foldin_max_hidden()} / {lib.tgcn_foldin_max_classes()}")
+            hs.append(h)
+            Cs.append(C)
+            _check_widths("FoldInLevels", h, C, at=f" level {l + 1}:")
         need = levels_lds_bytes(hs, Cs)
         if need > _lib.FOLDIN_LEVELS_LDS_LIMIT:
             raise NotImplementedError(f"FoldInLevels: the levels' W2 and Wh need {need} bytes of LDS next to the waves' slices, "
@@ -477,19 +482,13 @@ class FoldInLevels:
                 cut(hidden, self.h))
 
     def _composed(self, rowptr: Tensor, col: Tensor, val: Tensor, want_pred: bool):
-        """The same definition from the package's other pieces: the document scalars as `FoldIn._composed` takes them, ONE plan
-        of the [B, V] matrix of a_j per batch (the levels share it), ONE SpMM at the combined table's width, then per level
+        """The same definition from the package's other pieces: the document scalars and ONE plan of the [B, V] matrix
+        of a_j per batch (`_doc_scalars`; the levels share it), ONE SpMM at the combined table's width, then per level
         `dense.xw` for H_d Wh and u W2 and torch's softmax / arg-max for the link."""
-        B, V, L, dev = rowptr.numel() - 1, self.n_vocab, len(self.h), self.device
-        reference = self.degree_sum == "reference"
-        row = torch.repeat_interleave(torch.arange(B, device=dev), rowptr[1:] - rowptr[:-1])
-        c = col.long()
-        dis_d = gcn_norm_factors(torch.stack([c, row + V]), val, V + B, 1, self.degree_sum)[0][V:]
-        dw = self.dis[c]
-        a = (dw * val) * dis_d[row] if reference else val * (dw * dis_d[row])
-        a_dd = ((dis_d * 1.0) * dis_d).unsqueeze(1)
-        if c.numel():
-            sums = GraphPlan.from_coo(row, c, a, B, V, with_transpose=False).spmm(self._tab)
+        B, L, dev = rowptr.numel() - 1, len(self.h), self.device
+        a_dd, op = _doc_scalars(rowptr, col, val, self.dis, self.n_vocab, self.degree_sum)
+        if op is not None:
+            sums = op.spmm(self._tab)
         else:
             sums = torch.zeros(B, self._tab.size(1), dtype=torch.float32, device=dev)
         logits, links, hidden, preds = [], [], [], []

@@ -18,17 +18,20 @@ from .dense import _check_seed, new_seed
 from .plan import _stream_ptr, alloc_padded, colsum
 
 
-def _require(Z: Tensor, b: Tensor, W: Tensor, c: Optional[Tensor] = None) -> None:
+def _require_on_gpu(what: str, Z: Tensor, b: Tensor, W: Tensor, c: Optional[Tensor], note: str = "") -> None:
     """libtgcn.so only: anything else is an error, never a silent fallback."""
     for name, t in (("Z", Z), ("b", b), ("W", W), ("c", c)):
         if t is None:
             continue
         if not t.is_cuda:
-            raise RuntimeError(f"pytextgcn_amd: the fused MLP product needs `{name}` on an AMD GPU (it lives on "
+            raise RuntimeError(f"pytextgcn_amd: the {what} MLP product needs `{name}` on an AMD GPU (it lives on "
                                f"{t.device}); there is no CPU fallback")
         if t.dtype != torch.float32:
-            raise TypeError(f"pytextgcn_amd: the fused MLP product takes float32 operands, `{name}` is {t.dtype} "
-                            "(the reference casts the model with .float(), MLP_flat.py)")
+            raise TypeError(f"pytextgcn_amd: the {what} MLP product takes float32 operands, `{name}` is {t.dtype}{note}")
+
+
+def _require(Z: Tensor, b: Tensor, W: Tensor, c: Optional[Tensor] = None) -> None:
+    _require_on_gpu("fused", Z, b, W, c, " (the reference casts the model with .float(), MLP_flat.py)")
     if Z.dim() != 2 or W.dim() != 2 or b.dim() != 1 or Z.size(1) != b.size(0) or Z.size(1) != W.size(1) \
             or Z.size(1) == 0 or W.size(0) == 0 or (c is not None and (c.dim() != 1 or c.size(0) != W.size(0))):
         raise ValueError(f"act_linear: Z {tuple(Z.shape)} (N, k), b {tuple(b.shape)}, W {tuple(W.shape)} (n, k)"
@@ -46,83 +49,11 @@ def _seed_ptr(seed: Optional[Tensor], dev):
     return seed.data_ptr()
 
 
-def act_linear_forward(Z: Tensor, b: Tensor, W: Tensor, c: Optional[Tensor] = None, p: float = 0.0,
-                       seed: Optional[Tensor] = None, out: Optional[Tensor] = None, mask_row0: int = 0) -> Tensor:
-    """C [N, n] = dropout(selu(Z + b), p) @ W.t() (+ c); `seed` None (or p = 0): no mask.  No autograd."""
-    lib = _lib.load()
-    Z, W, b = _unit_cols(Z), _unit_cols(W), b.contiguous()
-    N, k = Z.shape
-    n = W.size(0)
-    C = alloc_padded(N, n, Z.device) if out is None else out
-    _lib.check(lib.tgcn_mlp_act_linear(Z.data_ptr(), max(Z.stride(0), k), b.data_ptr(), W.data_ptr(), max(W.stride(0), k),
-                                       c.contiguous().data_ptr() if c is not None else None, C.data_ptr(),
-                                       max(C.stride(0), n), N, k, n, float(p), _seed_ptr(seed, Z.device), int(mask_row0),
-                                       _stream_ptr(Z.device)))
-    return C
-
-
-def act_linear_backward(Z: Tensor, b: Tensor, W: Tensor, G: Tensor, p: float = 0.0, seed: Optional[Tensor] = None,
-                        want_z: bool = True, want_w: bool = True, mask_row0: int = 0):
-    """(dZ, db, dW) of `act_linear_forward` for G = dC; a pair that is not wanted comes back as None."""
-    if not (want_z or want_w):
-        return None, None, None
-    lib = _lib.load()
-    Z, W, b, G = _unit_cols(Z), _unit_cols(W), b.contiguous(), _unit_cols(G)
-    N, k = Z.shape
-    n = W.size(0)
-    dZ = alloc_padded(N, k, Z.device) if want_z else None
-    db = torch.empty(k, dtype=torch.float32, device=Z.device) if want_z else None
-    dW = torch.empty(n, k, dtype=torch.float32, device=Z.device) if want_w else None
-    ws = torch.empty(max(lib.tgcn_mlp_act_linear_grad_workspace_bytes(N, k, n), 16), dtype=torch.uint8, device=Z.device)
-    _lib.check(lib.tgcn_mlp_act_linear_grad(Z.data_ptr(), max(Z.stride(0), k), b.data_ptr(), W.data_ptr(),
-                                            max(W.stride(0), k), G.data_ptr(), max(G.stride(0), n),
-                                            dZ.data_ptr() if want_z else None, max(dZ.stride(0), k) if want_z else k,
-                                            db.data_ptr() if want_z else None, dW.data_ptr() if want_w else None, k, N, k,
-                                            n, float(p), _seed_ptr(seed, Z.device), int(mask_row0), ws.data_ptr(),
-                                            ws.numel(), _stream_ptr(Z.device)))
-    return dZ, db, dW
-
-
-class _ActLinear(torch.autograd.Function):
-    """Saves Z, b, W and the seed; the activation is recomputed where it is needed."""
-
-    @staticmethod
-    def forward(ctx, Z: Tensor, b: Tensor, W: Tensor, c: Optional[Tensor], p: float, seed: Optional[Tensor]):
-        ctx.p = p
-        ctx.has_seed = seed is not None
-        ctx.save_for_backward(Z, b, W, *([seed] if seed is not None else []))
-        return act_linear_forward(Z.detach(), b.detach(), W.detach(), None if c is None else c.detach(), p, seed)
-
-    @staticmethod
-    def backward(ctx, G: Tensor):
-        Z, b, W = ctx.saved_tensors[:3]
-        seed = ctx.saved_tensors[3] if ctx.has_seed else None
-        need = ctx.needs_input_grad
-        dZ, db, dW = act_linear_backward(Z, b, W, G, ctx.p, seed, want_z=need[0] or need[1], want_w=need[2])
-        dc = colsum(G) if need[3] else None
-        return (dZ if need[0] else None), (db if need[1] else None), dW, dc, None, None
-
-
-def act_linear(Z: Tensor, b: Tensor, W: Tensor, c: Optional[Tensor] = None, p: float = 0.0,
-               seed: Optional[Tensor] = None) -> Tensor:
-    """dropout(selu(Z + b), p) @ W.t() (+ c) with gradients for Z [N, k], b [k], W [n, k] and c [n].  p > 0 is
-    training-mode inverted dropout whose mask is a stateless hash of (seed, row, column) -- the library's random stream,
-    not torch's; `seed` None draws one from torch's generator on the device (`dense.new_seed`)."""
-    _require(Z, b, W, c)
-    p = float(p)
-    if not 0.0 <= p < 1.0:
-        raise ValueError(f"act_linear: dropout rate {p} outside [0, 1)")
-    if p == 0.0:
-        seed = None
-    elif seed is None:
-        seed = new_seed(Z.device)
-    return _ActLinear.apply(Z, b, W, c, p, seed)
-
-
 # ---------------------------------------------------------------------------------------------------------------------
-# The same product with a bias that depends on the ROW (libtgcn.so `tgcn_mlp_act_linear_cls*`): the one-hot class columns
-# that MLP_level.py appends to its features, as rows of a table T [Fh, k] picked by ids cls [N, S] (S = 1 or 2).  The
-# pre-activation is ((Z + T[cls[:, 0]]) + T[cls[:, 1]]) + b; an id outside [0, Fh) selects nothing.
+# The product with an optional bias that depends on the ROW (libtgcn.so `tgcn_mlp_act_linear_cls*`): the one-hot class
+# columns that MLP_level.py appends to its features, as rows of a table T [Fh, k] picked by ids cls [N, S] (S = 1 or 2).
+# The pre-activation is ((Z + T[cls[:, 0]]) + T[cls[:, 1]]) + b; an id outside [0, Fh) selects nothing.  One forward, one
+# backward and one autograd Function serve both forms: `term` is None or (cls, T), as the library's one nullable ClassTerm.
 # ---------------------------------------------------------------------------------------------------------------------
 MAX_CLASS_SLOTS = 2
 
@@ -143,29 +74,123 @@ def _require_cls(Z: Tensor, cls: Tensor, T: Tensor) -> None:
                          f"(Fh in 1..{max_class_rows()}, k) do not fit Z {tuple(Z.shape)} (N, k)")
 
 
-def _class_args(cls: Tensor, T: Tensor):
-    """(cls, T) with unit column strides and the seven arguments that describe them."""
-    cls, T = _unit_cols(cls), _unit_cols(T)
+def _class_args(Z: Tensor, term):
+    """(cls, T) checked against Z, with unit column strides, and the six arguments that describe them; `term` None: none."""
+    if term is None:
+        return None, ()
+    _require_cls(Z, *term)
+    cls, T = _unit_cols(term[0]), _unit_cols(term[1])
     S, (Fh, k) = cls.size(1), T.shape
-    return cls, T, (cls.data_ptr(), max(cls.stride(0), S), S, T.data_ptr(), max(T.stride(0), k), Fh)
+    return (cls, T), (cls.data_ptr(), max(cls.stride(0), S), S, T.data_ptr(), max(T.stride(0), k), Fh)
+
+
+def _forward(Z: Tensor, b: Tensor, W: Tensor, term, c: Optional[Tensor], p: float, seed: Optional[Tensor],
+             out: Optional[Tensor], mask_row0: int) -> Tensor:
+    lib = _lib.load()
+    term, term_args = _class_args(Z, term)         # (`term` keeps the unit-stride copies alive over the call)
+    Z, W, b = _unit_cols(Z), _unit_cols(W), b.contiguous()
+    N, k = Z.shape
+    n = W.size(0)
+    C = alloc_padded(N, n, Z.device) if out is None else out
+    fn = lib.tgcn_mlp_act_linear if term is None else lib.tgcn_mlp_act_linear_cls
+    _lib.check(fn(Z.data_ptr(), max(Z.stride(0), k), *term_args, b.data_ptr(), W.data_ptr(), max(W.stride(0), k),
+                  c.contiguous().data_ptr() if c is not None else None, C.data_ptr(), max(C.stride(0), n), N, k, n, float(p),
+                  _seed_ptr(seed, Z.device), int(mask_row0), _stream_ptr(Z.device)))
+    return C
+
+
+def _backward(Z: Tensor, b: Tensor, W: Tensor, term, G: Tensor, p: float, seed: Optional[Tensor], want_z: bool, want_w: bool,
+              want_t: bool, mask_row0: int):
+    """(dZ, db, dW, dT); dT comes with dZ: `want_t` implies `want_z`."""
+    want_z = want_z or want_t
+    if not (want_z or want_w):
+        return None, None, None, None
+    lib = _lib.load()
+    term, term_args = _class_args(Z, term)
+    Z, W, b, G = _unit_cols(Z), _unit_cols(W), b.contiguous(), _unit_cols(G)
+    N, k = Z.shape
+    n = W.size(0)
+    dev = Z.device
+    dZ = alloc_padded(N, k, dev) if want_z else None
+    db = torch.empty(k, dtype=torch.float32, device=dev) if want_z else None
+    dT = torch.empty(term[1].size(0), k, dtype=torch.float32, device=dev) if want_t else None
+    dW = torch.empty(n, k, dtype=torch.float32, device=dev) if want_w else None
+    if term is None:
+        fn, t_args, ws_bytes = lib.tgcn_mlp_act_linear_grad, (), lib.tgcn_mlp_act_linear_grad_workspace_bytes(N, k, n)
+    else:
+        fn, t_args = lib.tgcn_mlp_act_linear_cls_grad, (dT.data_ptr() if want_t else None, k)
+        ws_bytes = lib.tgcn_mlp_act_linear_cls_grad_workspace_bytes(N, k, n, term[1].size(0))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    _lib.check(fn(Z.data_ptr(), max(Z.stride(0), k), *term_args, b.data_ptr(), W.data_ptr(), max(W.stride(0), k), G.data_ptr(),
+                  max(G.stride(0), n), dZ.data_ptr() if want_z else None, max(dZ.stride(0), k) if want_z else k,
+                  db.data_ptr() if want_z else None, *t_args, dW.data_ptr() if want_w else None, k, N, k, n, float(p),
+                  _seed_ptr(seed, dev), int(mask_row0), ws.data_ptr(), ws.numel(), _stream_ptr(dev)))
+    return dZ, db, dW, dT
+
+
+class _ActLinear(torch.autograd.Function):
+    """Saves Z, b, W, the class term (when there is one) and the seed; the activation is recomputed where it is needed."""
+
+    @staticmethod
+    def forward(ctx, Z: Tensor, b: Tensor, W: Tensor, c: Optional[Tensor], cls: Optional[Tensor], T: Optional[Tensor],
+                p: float, seed: Optional[Tensor]):
+        ctx.p = p
+        ctx.has_term, ctx.has_seed = cls is not None, seed is not None
+        ctx.save_for_backward(Z, b, W, *([cls, T] if ctx.has_term else []), *([seed] if ctx.has_seed else []))
+        term = (cls, T.detach()) if ctx.has_term else None
+        return _forward(Z.detach(), b.detach(), W.detach(), term, None if c is None else c.detach(), p, seed, None, 0)
+
+    @staticmethod
+    def backward(ctx, G: Tensor):
+        saved = list(ctx.saved_tensors)
+        seed = saved.pop() if ctx.has_seed else None
+        Z, b, W = saved[:3]
+        term = tuple(saved[3:5]) if ctx.has_term else None
+        need = ctx.needs_input_grad
+        dZ, db, dW, dT = _backward(Z, b, W, term, G, ctx.p, seed, need[0] or need[1], need[2], need[5], 0)
+        dc = colsum(G) if need[3] else None
+        return (dZ if need[0] else None), (db if need[1] else None), dW, dc, None, dT, None, None
+
+
+def _apply(name: str, Z: Tensor, b: Tensor, W: Tensor, c: Optional[Tensor], term, p: float, seed: Optional[Tensor]) -> Tensor:
+    _require(Z, b, W, c)
+    if term is not None:
+        _require_cls(Z, *term)
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"{name}: dropout rate {p} outside [0, 1)")
+    if p == 0.0:
+        seed = None
+    elif seed is None:
+        seed = new_seed(Z.device)
+    return _ActLinear.apply(Z, b, W, c, *(term or (None, None)), p, seed)
+
+
+def act_linear_forward(Z: Tensor, b: Tensor, W: Tensor, c: Optional[Tensor] = None, p: float = 0.0,
+                       seed: Optional[Tensor] = None, out: Optional[Tensor] = None, mask_row0: int = 0) -> Tensor:
+    """C [N, n] = dropout(selu(Z + b), p) @ W.t() (+ c); `seed` None (or p = 0): no mask.  No autograd."""
+    return _forward(Z, b, W, None, c, p, seed, out, mask_row0)
+
+
+def act_linear_backward(Z: Tensor, b: Tensor, W: Tensor, G: Tensor, p: float = 0.0, seed: Optional[Tensor] = None,
+                        want_z: bool = True, want_w: bool = True, mask_row0: int = 0):
+    """(dZ, db, dW) of `act_linear_forward` for G = dC; a pair that is not wanted comes back as None."""
+    return _backward(Z, b, W, None, G, p, seed, want_z, want_w, False, mask_row0)[:3]
+
+
+def act_linear(Z: Tensor, b: Tensor, W: Tensor, c: Optional[Tensor] = None, p: float = 0.0,
+               seed: Optional[Tensor] = None) -> Tensor:
+    """dropout(selu(Z + b), p) @ W.t() (+ c) with gradients for Z [N, k], b [k], W [n, k] and c [n].  p > 0 is
+    training-mode inverted dropout whose mask is a stateless hash of (seed, row, column) -- the library's random stream,
+    not torch's; `seed` None draws one from torch's generator on the device (`dense.new_seed`)."""
+    return _apply("act_linear", Z, b, W, c, None, p, seed)
 
 
 def act_linear_cls_forward(Z: Tensor, b: Tensor, W: Tensor, cls: Tensor, T: Tensor, c: Optional[Tensor] = None,
                            p: float = 0.0, seed: Optional[Tensor] = None, out: Optional[Tensor] = None,
                            mask_row0: int = 0) -> Tensor:
     """C [N, n] = dropout(selu(Z + T[cls[:, 0]] (+ T[cls[:, 1]]) + b), p) @ W.t() (+ c).  No autograd."""
-    lib = _lib.load()
-    _require_cls(Z, cls, T)
-    Z, W, b = _unit_cols(Z), _unit_cols(W), b.contiguous()
-    cls, T, term = _class_args(cls, T)
-    N, k = Z.shape
-    n = W.size(0)
-    C = alloc_padded(N, n, Z.device) if out is None else out
-    _lib.check(lib.tgcn_mlp_act_linear_cls(Z.data_ptr(), max(Z.stride(0), k), *term, b.data_ptr(), W.data_ptr(),
-                                           max(W.stride(0), k), c.contiguous().data_ptr() if c is not None else None,
-                                           C.data_ptr(), max(C.stride(0), n), N, k, n, float(p), _seed_ptr(seed, Z.device),
-                                           int(mask_row0), _stream_ptr(Z.device)))
-    return C
+    return _forward(Z, b, W, (cls, T), c, p, seed, out, mask_row0)
 
 
 def act_linear_cls_backward(Z: Tensor, b: Tensor, W: Tensor, cls: Tensor, T: Tensor, G: Tensor, p: float = 0.0,
@@ -173,52 +198,7 @@ def act_linear_cls_backward(Z: Tensor, b: Tensor, W: Tensor, cls: Tensor, T: Ten
                             mask_row0: int = 0):
     """(dZ, db, dW, dT) of `act_linear_cls_forward` for G = dC; what is not wanted comes back as None.  dT [Fh, k] is the
     sum of dZ's rows per id (zero for a row of T that no id selects) and comes with dZ: `want_t` implies `want_z`."""
-    want_z = want_z or want_t
-    if not (want_z or want_w):
-        return None, None, None, None
-    lib = _lib.load()
-    _require_cls(Z, cls, T)
-    Z, W, b, G = _unit_cols(Z), _unit_cols(W), b.contiguous(), _unit_cols(G)
-    cls, T, term = _class_args(cls, T)
-    N, k = Z.shape
-    n, Fh = W.size(0), T.size(0)
-    dZ = alloc_padded(N, k, Z.device) if want_z else None
-    db = torch.empty(k, dtype=torch.float32, device=Z.device) if want_z else None
-    dT = torch.empty(Fh, k, dtype=torch.float32, device=Z.device) if want_t else None
-    dW = torch.empty(n, k, dtype=torch.float32, device=Z.device) if want_w else None
-    ws = torch.empty(max(lib.tgcn_mlp_act_linear_cls_grad_workspace_bytes(N, k, n, Fh), 16), dtype=torch.uint8,
-                     device=Z.device)
-    _lib.check(lib.tgcn_mlp_act_linear_cls_grad(Z.data_ptr(), max(Z.stride(0), k), *term, b.data_ptr(), W.data_ptr(),
-                                                max(W.stride(0), k), G.data_ptr(), max(G.stride(0), n),
-                                                dZ.data_ptr() if want_z else None, max(dZ.stride(0), k) if want_z else k,
-                                                db.data_ptr() if want_z else None, dT.data_ptr() if want_t else None, k,
-                                                dW.data_ptr() if want_w else None, k, N, k, n, float(p),
-                                                _seed_ptr(seed, Z.device), int(mask_row0), ws.data_ptr(), ws.numel(),
-                                                _stream_ptr(Z.device)))
-    return dZ, db, dW, dT
-
-
-class _ActLinearCls(torch.autograd.Function):
-    """`_ActLinear` with the class term: saves Z, b, W, cls, T and the seed."""
-
-    @staticmethod
-    def forward(ctx, Z: Tensor, b: Tensor, W: Tensor, c: Optional[Tensor], cls: Tensor, T: Tensor, p: float,
-                seed: Optional[Tensor]):
-        ctx.p = p
-        ctx.has_seed = seed is not None
-        ctx.save_for_backward(Z, b, W, cls, T, *([seed] if seed is not None else []))
-        return act_linear_cls_forward(Z.detach(), b.detach(), W.detach(), cls, T.detach(), None if c is None else c.detach(),
-                                      p, seed)
-
-    @staticmethod
-    def backward(ctx, G: Tensor):
-        Z, b, W, cls, T = ctx.saved_tensors[:5]
-        seed = ctx.saved_tensors[5] if ctx.has_seed else None
-        need = ctx.needs_input_grad
-        dZ, db, dW, dT = act_linear_cls_backward(Z, b, W, cls, T, G, ctx.p, seed, want_z=need[0] or need[1], want_w=need[2],
-                                                 want_t=need[5])
-        dc = colsum(G) if need[3] else None
-        return (dZ if need[0] else None), (db if need[1] else None), dW, dc, None, dT, None, None
+    return _backward(Z, b, W, (cls, T), G, p, seed, want_z, want_w, want_t, mask_row0)
 
 
 def act_linear_cls(Z: Tensor, b: Tensor, W: Tensor, c: Optional[Tensor], cls: Tensor, T: Tensor, p: float = 0.0,
@@ -226,16 +206,7 @@ def act_linear_cls(Z: Tensor, b: Tensor, W: Tensor, c: Optional[Tensor], cls: Te
     """`act_linear` on the pre-activation `Z + T[cls[:, 0]] (+ T[cls[:, 1]]) + b`, with gradients for Z [N, k], b [k],
     W [n, k], c [n] and T [Fh, k].  `cls` is int32 [N, 1] or [N, 2]; an id outside [0, Fh) selects nothing.  Dropout as in
     `act_linear`."""
-    _require(Z, b, W, c)
-    _require_cls(Z, cls, T)
-    p = float(p)
-    if not 0.0 <= p < 1.0:
-        raise ValueError(f"act_linear_cls: dropout rate {p} outside [0, 1)")
-    if p == 0.0:
-        seed = None
-    elif seed is None:
-        seed = new_seed(Z.device)
-    return _ActLinearCls.apply(Z, b, W, c, cls, T, p, seed)
+    return _apply("act_linear_cls", Z, b, W, c, (cls, T), p, seed)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -286,14 +257,7 @@ class GroupedLayout:
 
 
 def _require_grouped(Z: Tensor, b: Tensor, W: Tensor, c: Optional[Tensor], layout: GroupedLayout) -> None:
-    for name, t in (("Z", Z), ("b", b), ("W", W), ("c", c)):
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise RuntimeError(f"pytextgcn_amd: the grouped MLP product needs `{name}` on an AMD GPU (it lives on "
-                               f"{t.device}); there is no CPU fallback")
-        if t.dtype != torch.float32:
-            raise TypeError(f"pytextgcn_amd: the grouped MLP product takes float32 operands, `{name}` is {t.dtype}")
+    _require_on_gpu("grouped", Z, b, W, c)
     if not isinstance(layout, GroupedLayout) or layout.dev is None or layout.dev.device != Z.device:
         raise ValueError("grouped_act_linear: `layout` must be a GroupedLayout uploaded to the operands' device")
     if Z.dim() != 2 or W.dim() != 2 or b.dim() != 1 or Z.shape != (layout.N, layout.k) or W.shape != (layout.w_rows, layout.k) \
