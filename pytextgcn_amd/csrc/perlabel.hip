@@ -9,6 +9,10 @@
 //   loss_k  = mean over the selected rows r of group k of  lse(logits[r, seg_k]) - logits[r, seg_k.start + target[r]]
 //   loss    = sum of loss_k over the groups that have a selected row
 //   dlogits = (softmax over seg_k - one-hot) * inv_count[k] inside the row's segment, exactly 0.0f everywhere else
+// computed as ce_rows (masked_ce.h) computes the flat loss: with m the segment's maximum, e_c = exp(x_c - m) and `others`
+// the sum of the e_c without the target's e_t, a row's term is log(others + e_t) - (x_t - m) and its gradient is
+// e_c / sum off the target and -(others / sum) at it -- no `p_t - 1.f`, no `m + log(sum)`, which round a confident row's
+// gradient and a large row's loss away (tests/test_gpu_grouped_ce.py).
 //   pred[r] = seg_q.start + argmax logits[r, seg_q],  q = route[r]  (eval_perlabel.py:71-78: routed by the top label)
 //
 // k_grouped_ce (n_cols <= 256): LPR lanes hold one row, each lane four ABSOLUTE columns of it, whatever the row's segment:
@@ -158,20 +162,35 @@ __global__ __launch_bounds__(256) void k_grouped_ce(const GceArgs a) {
                     a.pred[r[u]] = p;
                 }
             }
-            float e[KPL], sum = 0.f;
+            // The arithmetic of ce_rows (masked_ce.h), restated for a segment of the row: the target's term is kept out of
+            // the sum of the others -- the gradient at the target is p_t - 1 = -(sum of the others) / sum, which
+            // `e_t / sum - 1.f` would round to a multiple of 2^-24, the size of the whole gradient row of a confident sample.
+            float e[KPL], others = 0.f, et = 0.f;
 #pragma unroll
             for (int k = 0; k < KPL; ++k) {
                 e[k] = in_t[k] ? expf(x[u][k] - m) : 0.f;
-                sum += e[k];
+                if (col(k) == tc[u])
+                    et = e[k];
+                else
+                    others += e[k];
             }
 #pragma unroll
-            for (int off = LPR / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+            for (int off = LPR / 2; off > 0; off >>= 1) others += __shfl_xor(others, off, 64);
+            // e_t from the lane that holds the target column (0 from any lane when there is no valid target)
+            et = __shfl(et, lane - sl + (tc[u] < 0 ? 0 : V4 ? tc[u] / KPL : tc[u] % LPR), 64);
+            const float sum = others + et;
             if (on[u]) {
-                const float lse = m + logf(sum);
-                // the lane that holds the target logit adds the row's term to its sub-group's slot of the row's group
+                // the lane that holds the target logit adds the row's term, log(sum) - (x_t - m), to its sub-group's slot of
+                // the row's group: the difference first, so that a row at +-1e4 does not round its term to fp32's spacing there
+                // (one update of the slot behind the column loop: hipcc 7 rejects its own code for the 16-byte
+                // instantiations when the update sits inside it)
+                const float lsum = logf(sum);
+                float term = 0.f;
+                bool mine_t = false;
 #pragma unroll
                 for (int k = 0; k < KPL; ++k)
-                    if (col(k) == tc[u]) mine[g[u]] += lse - x[u][k];
+                    if (col(k) == tc[u]) term = lsum - (x[u][k] - m), mine_t = true;
+                if (mine_t) mine[g[u]] += term;
                 // a class index outside the segment poisons the group's loss instead of being dropped silently
                 // (torch raises; the Python wrapper checks the labels once per tensor)
                 if (bad[u] && sl == 0) mine[g[u]] = NAN;
@@ -183,7 +202,7 @@ __global__ __launch_bounds__(256) void k_grouped_ce(const GceArgs a) {
                 float d[KPL];
 #pragma unroll
                 for (int k = 0; k < KPL; ++k) {
-                    d[k] = in_t[k] ? (e[k] * inv - (col(k) == tc[u] ? 1.f : 0.f)) * ic : 0.f;
+                    d[k] = in_t[k] ? (col(k) == tc[u] ? -(others * inv) : e[k] * inv) * ic : 0.f;
                     cs[k] += d[k];
                 }
                 if constexpr (V4) {
@@ -264,28 +283,30 @@ __global__ __launch_bounds__(256) void k_grouped_ce_wide(const GceArgs a) {
             for (int c = s0 + lane; c < s1; c += 64) m = fmaxf(m, row[c]);
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+            // as on the register path: the target's term apart from the sum of the others, differences from the row
+            // maximum before anything is added to log(sum)
+            const int64_t t = on ? a.target[r] : 0;
+            const bool bad = on && (t < 0 || t >= s1 - s0);
+            const int tc = (on && !bad) ? s0 + static_cast<int>(t) : -1;      // (no read outside the segment)
+            const float xt = tc >= 0 ? row[tc] - m : 0.f;
             float s = 0.f;
-            for (int c = s0 + lane; c < s1; c += 64) s += expf(row[c] - m);
+            for (int c = s0 + lane; c < s1; c += 64)
+                if (c != tc) s += expf(row[c] - m);
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-            const float lse = m + logf(s);
-            int tc = -1;
-            if (on) {
-                const int64_t t = a.target[r];
-                const bool bad = t < 0 || t >= s1 - s0;
-                tc = bad ? -1 : s0 + static_cast<int>(t);
-                if (lane == 0) {
-                    if (bad)
-                        mine[g] = NAN;
-                    else
-                        mine[g] += lse - row[tc];
-                }
+            const float sum = s + (tc >= 0 ? expf(xt) : 0.f);
+            if (on && lane == 0) {
+                if (bad)
+                    mine[g] = NAN;
+                else
+                    mine[g] += logf(sum) - xt;
             }
             if (a.dlogits != nullptr) {
                 float *drow = a.dlogits + r * a.ldd;
                 const float ic = on ? a.inv_count[g] : 0.f;
+                const float inv = on ? 1.f / sum : 0.f;
                 for (int c = lane; c < C; c += 64)
-                    drow[c] = (c >= s0 && c < s1) ? (expf(row[c] - lse) - (c == tc ? 1.f : 0.f)) * ic : 0.f;
+                    drow[c] = (c >= s0 && c < s1) ? (c == tc ? -(s * inv) : expf(row[c] - m) * inv) * ic : 0.f;
             }
         }
     }
