@@ -1350,87 +1350,102 @@ int tn_blocks(int64_t N) {
 
 constexpr int kTallMaxGrid = 256 * 4 * 2;   // upper bound of the persistent grid (CUs x resident workgroups), sizes colpart
 
-template <bool TRANS_B, bool DROP, bool COLSUM = false>
-int launch_tall_one(const float *A, int64_t lda, const float *B, int64_t ldb, float *C, int64_t ldc,
-                    int64_t N, int k, int n, const Drop drop, hipStream_t s, float *colpart, float *colsum,
-                    const Place place) {
-    const int nt = (n + 31) / 32;
-    const int kpad = (k + 7) & ~7;
-    size_t lds_bytes = sizeof(float) * (static_cast<size_t>(kpad) * (32 * nt) + (COLSUM ? 4 * 32 * nt : 0));
-    int grid_used = 0;
-    if (lds_bytes > 160 * 1024 || nt > 8) {
-        set_error("tgcn_gemm: the small operand (%d x %d) does not fit the 160 KB LDS", k, n);
-        return TGCN_E_INVALID;
+// Host side.  pick_tall / pick_tn say which kernel a launch takes, what it reserves and how many workgroups share a CU;
+// `launch` is the only place a kernel of this file is started; the launchers below turn a leaf into its instantiation.
+inline bool aligned16(const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+
+// compute units of the current device (256 when it cannot be asked)
+int cu_count() {
+    // hipGetDeviceProperties fills a large struct (tens of microseconds): asked once per device
+    static std::atomic<int> cached[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    int v = cached[dev].load(std::memory_order_relaxed);
+    if (v == 0) {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, dev) == hipSuccess) v = prop.multiProcessorCount;
+        if (v > 0) cached[dev].store(v, std::memory_order_relaxed);
     }
-    const int64_t n_blocks = (N + 31) / 32;
-    // persistent workgroups: exactly one resident set (a second, partial round of workgroups would
-    // leave most CUs idle at the end)
-    int n_cu = 256;
-    {
-        // hipGetDeviceProperties fills a large struct (tens of microseconds): asked once per device
-        static std::atomic<int> cached[64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
-            int v = cached[dev].load(std::memory_order_relaxed);
-            if (v == 0) {
-                hipDeviceProp_t prop;
-                if (hipGetDeviceProperties(&prop, dev) == hipSuccess) v = prop.multiProcessorCount;
-                if (v > 0) cached[dev].store(v, std::memory_order_relaxed);
-            }
-            if (v > 0) n_cu = v;
-        }
-    }
-#define TGCN_TALL_K(NT, K8, NQ_) TGCN_TALL_KB(NT, K8, NQ_, false)
-#define TGCN_TALL_KB(NT, K8, NQ_, BI)                                                                \
-    do {                                                                                          \
-        const void *fn = reinterpret_cast<const void *>(&k_gemm_tall<NT, TRANS_B, K8, NQ_, DROP, COLSUM, BI>); \
-        TGCN_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,        \
-                                           static_cast<int>(lds_bytes)));                         \
-        int per_cu = 1;                                                                           \
-        TGCN_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds_bytes)); \
-        per_cu = std::max(1, std::min(per_cu, 4));                                                \
-        const int grid = static_cast<int>(std::max<int64_t>(                                      \
-            1, std::min<int64_t>({(n_blocks + 3) / 4, int64_t(n_cu) * per_cu, int64_t(kTallMaxGrid)}))); \
-        grid_used = grid;                                                                         \
-        k_gemm_tall<NT, TRANS_B, K8, NQ_, DROP, COLSUM, BI><<<grid, 256, lds_bytes, s>>>(A, lda, B, ldb, C, ldc, N, k, n, \
-                                                                                         drop, colpart, place); \
-    } while (0)
-#define TGCN_TALL(NT)                                                                             \
-    do {                                                                                          \
-        if (k % 8 == 0)                                                                           \
-            TGCN_TALL_K(NT, true, 0);                                                             \
-        else                                                                                      \
-            TGCN_TALL_K(NT, false, 0);                                                            \
-    } while (0)
-    // the two shapes of the GCN layers get fully unrolled k-loops (hidden width 200, class width 64)
-    auto finish = [&]() -> int {
-        TGCN_HIP_CHECK(hipGetLastError());
-        if constexpr (COLSUM) return launch_colsum_final(colpart, grid_used, n, colsum, s);
-        return TGCN_OK;
+    return v > 0 ? v : 256;
+}
+
+// Every launch: the kernel's dynamic-LDS limit (on every call that reserves any), the launch, its status.
+template <class... P, class... Args>
+int launch(void (*kernel)(P...), int grid, int block, size_t lds, hipStream_t s, const Args &...args) {
+    if (lds != 0)
+        TGCN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+    kernel<<<grid, block, lds, s>>>(args...);
+    TGCN_HIP_CHECK(hipGetLastError());
+    return TGCN_OK;
+}
+
+// A run-time value as a compile-time one: f(std::integral_constant<int, V>{}) for the V that equals v / f(std::true_type or
+// std::false_type).  Only the listed values are instantiated.
+template <int V>
+constexpr std::integral_constant<int, V> int_c{};
+constexpr std::true_type yes{};
+constexpr std::false_type no{};
+
+template <int... V, class F>
+int with_int(int v, F &&f) {
+    int rc = TGCN_E_INVALID;
+    if (!(... || (v == V ? (rc = f(int_c<V>), true) : false))) set_error("tgcn_gemm: no kernel for a tile count of %d", v);
+    return rc;
+}
+
+template <class F>
+int with_bool(bool b, F &&f) { return b ? f(yes) : f(no); }
+
+// The small operand of a tall product in LDS: [round_up(k, 8)][32 nt] floats, and four rows of column sums behind it.
+inline size_t tall_image_bytes(int k, int n, bool colsum) {
+    const size_t kpad = (k + 7) & ~7, npad = 32 * ((n + 31) / 32);
+    return sizeof(float) * (kpad * npad + (colsum ? 4 * npad : 0));
+}
+
+enum class TallFamily { tall, pipe, split };    // k_gemm_tall, k_gemm_pipe, k_gemm_tall_split
+
+struct TallCall {                    // what pick_tall is told about one launch
+    bool trans_b, drop, colsum;      // the product form
+    int k, n;
+    int64_t lda, ldc;
+    bool a16, c16;                   // A / C 16-byte aligned
+    const uint32_t *bits; int64_t bits_stride;       // Drop::bits and its stride
+    Place place;
+    bool split;                      // tgcn_set_gemm_split
+    bool one_per_cu;                 // TGCN_TALL_ONE_PER_CU (on unless "0")
+};
+
+struct TallLeaf {
+    TallFamily family;
+    int nt;            // column tiles of 32
+    bool k8;           // k % 8 == 0
+    int nq;            // unrolled k steps (0: the generic loop)
+    bool bits;         // the mask on the result comes from the record
+    bool row_store;    // split only: whole rows of C leave through LDS
+    size_t lds;        // dynamic LDS the launch reserves (more than half of the CU's 160 KB keeps a second workgroup off)
+    int per_cu;        // workgroups per CU the grid counts on: 1, 2, or 0 = what the occupancy calculator allows, at most 4
+    int block;         // threads per workgroup
+};
+
+// Which kernel one launch of a tall product takes.  One chain, first match wins.
+TallLeaf pick_tall(const TallCall &c) {
+    const int nt = (c.n + 31) / 32;
+    const size_t image = tall_image_bytes(c.k, c.n, c.colsum);
+    const bool one_chunk = c.place.k0 == 0 && !c.place.accum;
+    const bool whole = c.place.col0 == 0 && one_chunk;                      // not a piece of a larger product
+    // the mask from the forward product's record: n in (192, 256] has four words per row half (16-byte reads)
+    const bool from_record = c.drop && c.bits && c.n > 192 && c.bits_stride % 4 == 0 && aligned16(c.bits);
+    auto tall = [&](bool k8, int nq, bool bits, size_t lds) {
+        return TallLeaf{TallFamily::tall, nt, k8, nq, bits, false, lds, 0, 256};
     };
-    const bool whole = place.col0 == 0 && place.k0 == 0 && !place.accum;      // not a piece of a larger product
-    if (whole && g_gemm_split.load(std::memory_order_relaxed) != 0 && lda % 4 == 0) {
-        // split-bf16 products for the two shapes of the GCN layers (everything else keeps the fp32 MFMA kernels)
-#define TGCN_SPLIT(NT, NQ_)                                                                                         \
-    do {                                                                                                            \
-        const bool rs = TRANS_B && ldc == n && n % 4 == 0 && reinterpret_cast<uintptr_t>(C) % 16 == 0;              \
-        const size_t lb = size_t(3) * NQ_ * 2 * (32 * NT) * 16 + (rs ? size_t(kSplitWaves) * 8 * (32 * NT) * 4 : 0); \
-        const void *fn = reinterpret_cast<const void *>(&k_gemm_tall_split<NT, TRANS_B, NQ_, DROP, COLSUM>);        \
-        TGCN_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lb))); \
-        const int grid = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>({(n_blocks + kSplitWaves - 1) / kSplitWaves, int64_t(n_cu), int64_t(kTallMaxGrid)}))); \
-        grid_used = grid;                                                                                           \
-        k_gemm_tall_split<NT, TRANS_B, NQ_, DROP, COLSUM><<<grid, 64 * kSplitWaves, lb, s>>>(A, lda, B, ldb, C, ldc, N, k, n, \
-                                                                                            drop, colpart, rs);     \
-    } while (0)
-        if (!TRANS_B && !COLSUM && k == 200 && nt == 2) {
-            TGCN_SPLIT(2, 13);
-            return finish();
-        }
-        if (TRANS_B && k == 64 && nt == 7) {
-            TGCN_SPLIT(7, 4);
-            return finish();
-        }
-#undef TGCN_SPLIT
+    // split-bf16 products for the two shapes of the GCN layers (everything else keeps the fp32 MFMA kernels)
+    const bool split_nn = !c.trans_b && !c.colsum && c.k == 200 && nt == 2, split_nt = c.trans_b && c.k == 64 && nt == 7;
+    if (whole && c.split && c.lda % 4 == 0 && (split_nn || split_nt)) {
+        const int nq = split_nn ? 13 : 4;
+        const bool rs = c.trans_b && c.ldc == c.n && c.n % 4 == 0 && c.c16;
+        const size_t lds = size_t(3) * nq * 2 * (32 * nt) * 16 + (rs ? size_t(kSplitWaves) * 8 * (32 * nt) * 4 : 0);
+        return {TallFamily::split, nt, true, nq, false, rs, lds, 1, 64 * kSplitWaves};
     }
     // ONE resident workgroup per CU for the two GCN shapes when nothing is hashed: measured at c4 (tools/ab_dense.py), with
     // a second workgroup kept off the CU by reserving more than half of its LDS -- nt 0.67 -> 0.59 ms, nt + column sums
@@ -1439,95 +1454,92 @@ int launch_tall_one(const float *A, int64_t lda, const float *B, int64_t ldb, fl
     // its mask from the record: its epilogue still works on every element (an LDS read, a multiply, two bit operations:
     // 0.12 ms when nothing overlaps it), which a second workgroup hides.
     // TGCN_TALL_ONE_PER_CU=0 (diagnostic, read once): let as many workgroups onto a CU as fit, as before round 4
+    const size_t alone = std::max<size_t>(image, c.one_per_cu ? 82 * 1024 : 0);
+    // the two shapes of the GCN layers get fully unrolled k-loops (hidden width 200, class width 64)
+    if (!c.trans_b && whole && c.k == 200 && nt == 2) return tall(true, 25, false, c.drop ? image : alone);
+    // a column group of a wider layer at the hidden width 200 (DBpedia's 219 classes = 128 + 91 columns): the fully
+    // unrolled k-loop with the counted load ring, as the GCN shape has it (the generic loop leaves 8 MFMAs of cover)
+    if (!c.trans_b && c.k == 200 && one_chunk && (nt == 4 || nt == 3)) return tall(true, 25, false, image);
+    // a column group of the input-gradient product of a 217 .. 224-class layer (DBpedia l3: 219; hidden 200 = 128 + 72
+    // result columns): 28 unrolled steps with the load ring; needs the operand's rows to reach round_up(k, 4) (the
+    // zero-padded gradient buffer) so that the last piece of a row is read inside it
+    if (c.trans_b && c.k > 216 && c.k <= 224 && one_chunk && (nt == 4 || nt == 3) && c.lda >= ((c.k + 3) & ~3))
+        return tall(c.k % 8 == 0, 28, false, image);
+    if (c.trans_b && whole && c.k == 64 && nt == 7) {
+        // the block-pipelined kernel (k_gemm_pipe): plain / column sums / mask from the record.
+        // Workgroups per CU, measured at c4 (tools/ab_dense.py, profiles/r05_ab_dense.log): the unmasked kernels want the CU
+        // to themselves (nt 0.515 against 0.565 ms with two, nt + column sums 0.53 / 0.59); the one that masks its result
+        // from the record has ~450 vector-ALU instructions of epilogue per block, which a second workgroup's MFMAs hide
+        // (0.59 against 0.625 ms).  k_gemm_tall, the kernel this replaces: 0.585 / 0.58 / 0.665 ms.
+        if (TGCN_NT_PIPE && c.lda % 4 == 0 && c.a16 && (!c.drop || from_record))
+            return from_record ? TallLeaf{TallFamily::pipe, 7, true, 8, true, false, image + 4 * 1024, 2, 256}
+                               : TallLeaf{TallFamily::pipe, 7, true, 8, false, false, alone, 1, 256};
+        // + the waves' mask slices; two workgroups per CU (one: 0.71 ms, two: 0.68)
+        if (from_record) return tall(true, 8, true, image + 4 * 1024);
+        return tall(true, 8, false, c.drop ? image : alone);
+    }
+    return tall(c.k % 8 == 0, 0, false, image);
+}
+
+// One launch of a tall product: the leaf, its grid -- persistent workgroups, exactly one resident set (a second, partial
+// round would leave most CUs idle at the end) -- and the leaf's instantiation, out of the kernels this file builds.
+template <bool TRANS_B, bool DROP, bool COLSUM = false>
+int launch_tall_one(const float *A, int64_t lda, const float *B, int64_t ldb, float *C, int64_t ldc,
+                    int64_t N, int k, int n, const Drop drop, hipStream_t s, float *colpart, float *colsum,
+                    const Place place) {
+    if (tall_image_bytes(k, n, COLSUM) > 160 * 1024 || n > 256) {
+        set_error("tgcn_gemm: the small operand (%d x %d) does not fit the 160 KB LDS", k, n);
+        return TGCN_E_INVALID;
+    }
     static const bool one_per_cu = [] {
         const char *e = std::getenv("TGCN_TALL_ONE_PER_CU");
         return !(e && e[0] == '0');
     }();
-    const size_t kOnePerCu = one_per_cu ? 82 * 1024 : 0;
-    if constexpr (!TRANS_B) {
-        if (whole && k == 200 && nt == 2) {
-            if constexpr (!DROP) lds_bytes = std::max(lds_bytes, kOnePerCu);
-            TGCN_TALL_K(2, true, 25);
-            return finish();
+    const TallLeaf l = pick_tall({TRANS_B, DROP, COLSUM, k, n, lda, ldc, aligned16(A), aligned16(C), drop.bits,
+                                  drop.bits_stride, place, g_gemm_split.load(std::memory_order_relaxed) != 0, one_per_cu});
+    // `tail`: the kernel's arguments behind (A, lda, B, ldb, C, ldc, N)
+    auto go = [&](auto *kernel, const auto &...tail) -> int {
+        int per_cu = l.per_cu;
+        if (per_cu == 0) {
+            TGCN_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(kernel),
+                                                                        l.block, l.lds));
+            per_cu = std::max(1, std::min(per_cu, 4));
         }
-    }
-    if constexpr (!TRANS_B) {
-        // a column group of a wider layer at the hidden width 200 (DBpedia's 219 classes = 128 + 91 columns): the fully
-        // unrolled k-loop with the counted load ring, as the GCN shape has it (the generic loop leaves 8 MFMAs of cover)
-        if (k == 200 && place.k0 == 0 && !place.accum && (nt == 4 || nt == 3)) {
-            if (nt == 4) TGCN_TALL_K(4, true, 25); else TGCN_TALL_K(3, true, 25);
-            return finish();
-        }
-    }
-    if constexpr (TRANS_B) {
-        // a column group of the input-gradient product of a 217 .. 224-class layer (DBpedia l3: 219; hidden 200 = 128 + 72
-        // result columns): 28 unrolled steps with the load ring; needs the operand's rows to reach round_up(k, 4) (the
-        // zero-padded gradient buffer) so that the last piece of a row is read inside it
-        if (k > 216 && k <= 224 && place.k0 == 0 && !place.accum && (nt == 4 || nt == 3) && lda >= ((k + 3) & ~3)) {
-            if (k % 8 == 0) {
-                if (nt == 4) TGCN_TALL_K(4, true, 28); else TGCN_TALL_K(3, true, 28);
-            } else {
-                if (nt == 4) TGCN_TALL_K(4, false, 28); else TGCN_TALL_K(3, false, 28);
-            }
-            return finish();
-        }
+        const int64_t waves = l.block / 64, n_blocks = (N + 31) / 32;       // a wave takes 32 rows at a time
+        const int grid = static_cast<int>(std::max<int64_t>(
+            1, std::min<int64_t>({(n_blocks + waves - 1) / waves, int64_t(cu_count()) * per_cu, int64_t(kTallMaxGrid)})));
+        TGCN_CHECK(launch(kernel, grid, l.block, l.lds, s, A, lda, B, ldb, C, ldc, N, tail...));
+        if constexpr (COLSUM) return launch_colsum_final(colpart, grid, n, colsum, s);
+        return TGCN_OK;
+    };
+    auto tall = [&](auto NT, auto K8, auto NQ, auto BI) {
+        return go(&k_gemm_tall<NT(), TRANS_B, K8(), NQ(), DROP, COLSUM, BI()>, k, n, drop, colpart, place);
+    };
+    auto split = [&](auto NT, auto NQ) {
+        return go(&k_gemm_tall_split<NT(), TRANS_B, NQ(), DROP, COLSUM>, k, n, drop, colpart, l.row_store);
+    };
+    if (l.family == TallFamily::split) return l.nt == 2 ? split(int_c<2>, int_c<13>) : split(int_c<7>, int_c<4>);
 #if TGCN_NT_PIPE
-    if (whole && k == 64 && nt == 7 && lda % 4 == 0 && reinterpret_cast<uintptr_t>(A) % 16 == 0) {
-        // the block-pipelined kernel (k_gemm_pipe): plain / column sums / mask from the record
-        const bool from_record = DROP && drop.bits && n > 192 && drop.bits_stride % 4 == 0 &&
-                                 reinterpret_cast<uintptr_t>(drop.bits) % 16 == 0;
-        if (!DROP || from_record) {
-            size_t lb = sizeof(float) * (size_t(64) * 224 + (COLSUM ? 4 * 224 : 0)) + (from_record ? 4 * 1024 : 0);
-            // Workgroups per CU, measured at c4 (tools/ab_dense.py, profiles/r05_ab_dense.log): the unmasked kernels want the CU
-            // to themselves (nt 0.515 against 0.565 ms with two, nt + column sums 0.53 / 0.59); the one that masks its result
-            // from the record has ~450 vector-ALU instructions of epilogue per block, which a second workgroup's MFMAs hide
-            // (0.59 against 0.625 ms).  k_gemm_tall, the kernel this replaces: 0.585 / 0.58 / 0.665 ms.
-            const int pipe_per_cu = from_record ? 2 : 1;
-            if (pipe_per_cu == 1) lb = std::max(lb, kOnePerCu);
-            const int grid = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>({(n_blocks + 3) / 4, int64_t(n_cu) * pipe_per_cu,
-                                                                                      int64_t(kTallMaxGrid)})));
-            grid_used = grid;
-#define TGCN_PIPE(BI)                                                                                              \
-    do {                                                                                                           \
-        const void *fn = reinterpret_cast<const void *>(&k_gemm_pipe<7, 8, true, COLSUM, BI>);                     \
-        TGCN_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lb))); \
-        k_gemm_pipe<7, 8, true, COLSUM, BI><<<grid, 256, lb, s>>>(A, lda, B, ldb, C, ldc, N, n, drop, colpart);   \
-    } while (0)
-            if (from_record) TGCN_PIPE(true); else TGCN_PIPE(false);
-#undef TGCN_PIPE
-            return finish();
-        }
-    }
+    if (l.family == TallFamily::pipe)
+        return with_bool(l.bits, [&](auto BI) { return go(&k_gemm_pipe<7, 8, true, COLSUM, BI()>, n, drop, colpart); });
 #endif
-    if (whole && k == 64 && nt == 7) {
-        if constexpr (DROP) {
-            // the mask from the forward product's record: n in (192, 256] has four words per row half (16-byte reads)
-            if (drop.bits && n > 192 && drop.bits_stride % 4 == 0 && reinterpret_cast<uintptr_t>(drop.bits) % 16 == 0) {
-                lds_bytes += 4 * 1024;                  // the waves' mask slices; two workgroups per CU (one: 0.71 ms, two: 0.68)
-                TGCN_TALL_KB(7, true, 8, true);
-                return finish();
-            }
-        } else {
-            lds_bytes = std::max(lds_bytes, kOnePerCu);
-        }
-        TGCN_TALL_K(7, true, 8);
-        return finish();
+    if (l.nq == 0)
+        return with_int<1, 2, 3, 4, 5, 6, 7, 8>(l.nt, [&](auto NT) {
+            return with_bool(l.k8, [&](auto K8) { return tall(NT, K8, int_c<0>, no); });
+        });
+    if constexpr (!TRANS_B) {
+        if (l.nq == 25) return with_int<2, 3, 4>(l.nt, [&](auto NT) { return tall(NT, yes, int_c<25>, no); });
+    } else {
+        if (l.nq == 28)
+            return with_int<3, 4>(l.nt, [&](auto NT) {
+                return with_bool(l.k8, [&](auto K8) { return tall(NT, K8, int_c<28>, no); });
+            });
+        if constexpr (DROP)
+            if (l.nq == 8 && l.bits) return tall(int_c<7>, yes, int_c<8>, yes);
+        if (l.nq == 8) return tall(int_c<7>, yes, int_c<8>, no);
     }
-    }
-    switch (nt) {
-        case 1: TGCN_TALL(1); break;
-        case 2: TGCN_TALL(2); break;
-        case 3: TGCN_TALL(3); break;
-        case 4: TGCN_TALL(4); break;
-        case 5: TGCN_TALL(5); break;
-        case 6: TGCN_TALL(6); break;
-        case 7: TGCN_TALL(7); break;
-        default: TGCN_TALL(8); break;
-    }
-#undef TGCN_TALL
-#undef TGCN_TALL_K
-#undef TGCN_TALL_KB
-    return finish();
+    set_error("tgcn_gemm: no kernel for %d tiles with %d unrolled steps", l.nt, l.nq);
+    return TGCN_E_INVALID;
 }
 
 // The whole product: one launch when the small operand (k x n, padded) fits the LDS, otherwise column groups of
@@ -1538,8 +1550,7 @@ template <bool TRANS_B, bool DROP, bool COLSUM = false>
 int launch_tall(const float *A, int64_t lda, const float *B, int64_t ldb, float *C, int64_t ldc,
                 int64_t N, int k, int n, const Drop drop, hipStream_t s, float *colpart = nullptr,
                 float *colsum = nullptr) {
-    const int kpad = (k + 7) & ~7, npad = 32 * ((n + 31) / 32);
-    if (npad <= 256 && sizeof(float) * (size_t(kpad) * npad + (COLSUM ? 4 * npad : 0)) <= 160 * 1024)
+    if (n <= 256 && tall_image_bytes(k, n, COLSUM) <= 160 * 1024)
         return launch_tall_one<TRANS_B, DROP, COLSUM>(A, lda, B, ldb, C, ldc, N, k, n, drop, s, colpart, colsum,
                                                       Place{0, 0, 0});
     for (int j0 = 0; j0 < n; j0 += kGroupCols) {
@@ -1563,6 +1574,51 @@ int launch_tall(const float *A, int64_t lda, const float *B, int64_t ldb, float 
     return TGCN_OK;
 }
 
+enum class TnFamily { partial, staged, split };    // k_gemm_tn_partial, k_gemm_tn_staged, k_gemm_tn_split
+
+struct TnCall {                      // what pick_tn is told about one launch: columns [i0, i0 + kg) of A, [j0, j0 + ng) of G
+    bool drop, record;               // a mask on A; its record (Drop::bits) is at hand
+    int64_t N;
+    int k;                           // all columns of A
+    int i0, kg, j0, ng;
+    int64_t lda, ldg;
+    bool a16, g16;                   // A + i0 / G + j0 16-byte aligned
+    bool split;                      // tgcn_set_gemm_split
+};
+
+struct TnLeaf {
+    TnFamily family;
+    int nt;            // column tiles of G the kernel and the reduction work on (staged: three run as four)
+    int mt;            // M-tiles (32 columns of A); staged: the kernel's bucket 2 / 4 / 7 / 8
+    bool bits;         // staged with a mask: the keep decisions come from the record
+    size_t lds;        // dynamic LDS
+    int64_t rpw;       // rows per workgroup, rounded up to the kernel's step
+    int cols;          // columns of G the kernel is told about
+};
+
+// Which kernel one launch of the tn product takes; every family runs tn_blocks(N) workgroups of 256 threads, two to a CU.
+TnLeaf pick_tn(const TnCall &c) {
+    const int nb = tn_blocks(c.N);
+    const int64_t rows = (c.N + nb - 1) / nb;
+    const int nt = (c.ng + 31) / 32, mt = (c.kg + 31) / 32;
+    // split-bf16 products for the weight gradient of the GCN's second layer (16-row K steps through LDS), contiguous only
+    if (c.split && c.kg == 200 && nt == 2 && c.lda == c.kg && c.ldg == c.ng && c.ng % 4 == 0 && c.a16 && c.g16)
+        return {TnFamily::split, nt, mt, false, sizeof(float) * 2 * (32 * (c.kg + 4) + 32 * (c.ng + 4)),
+                (rows + 31) & ~int64_t(31), c.ng};
+    // 16-byte friendly operands with 1, 2 or 4 column tiles of G: the LDS-staged kernel (rows split over the waves)
+    // A width that is not a multiple of 4 (DBpedia's 219 classes: the second group holds 91 columns) is served when
+    // the row reaches to the next multiple of 4 -- a zero-padded buffer (plan.alloc_padded), or columns of a wider
+    // matrix: what is read there lands in result columns nobody stores.  Three tiles run as four.
+    const int ng4 = (c.ng + 3) & ~3, nts = nt == 3 ? 4 : nt;
+    if ((nts == 1 || nts == 2 || nts == 4) && c.kg % 4 == 0 && c.lda % 4 == 0 && c.ldg % 4 == 0 &&
+        int64_t(c.j0) + ng4 <= c.ldg && c.a16 && c.g16 && tn_staged_lds_bytes(c.kg, ng4) <= 160 * 1024 &&
+        std::getenv("TGCN_TN_STAGED_OFF") == nullptr)                       // (read at call time)
+        // the recorded mask describes whole rows of A: usable when this launch covers all k columns
+        return {TnFamily::staged, nts, mt <= 2 ? 2 : mt <= 4 ? 4 : mt <= 7 ? 7 : 8, c.record && c.i0 == 0 && c.kg == c.k,
+                tn_staged_lds_bytes(c.kg, ng4), (rows + kTnStageRows - 1) / kTnStageRows * kTnStageRows, ng4};
+    return {TnFamily::partial, nt, mt, false, 0, (rows + 1) & ~int64_t(1), c.ng};    // even: steps are row pairs
+}
+
 int check_common(const char *fn, const void *a, const void *b, const void *c, int64_t N, int k, int n) {
     if (!a || !b || !c || N < 0 || k <= 0 || n <= 0) {
         set_error("%s: bad argument (N=%lld k=%d n=%d)", fn, (long long)N, k, n);
@@ -1580,7 +1636,7 @@ static int gemm_nn_impl(const char *fn, const float *A, int64_t lda, const float
                         int64_t ldc, int64_t N, int k, int n, const tgcn::Drop *drop, tgcn_stream stream) {
     using namespace tgcn;
     TGCN_CHECK(check_common(fn, A, B, C, N, k, n));
-    if (lda < k || ldb < n || ldc < n || lda % 4 != 0 || reinterpret_cast<uintptr_t>(A) % 16 != 0) {
+    if (lda < k || ldb < n || ldc < n || lda % 4 != 0 || !aligned16(A)) {
         set_error("%s: need lda >= k, ldb, ldc >= n, lda %% 4 == 0 and A 16-byte aligned", fn);
         return TGCN_E_INVALID;
     }
@@ -1595,7 +1651,7 @@ static int gemm_nt_impl(const char *fn, const float *A, int64_t lda, const float
                         float *colsum = nullptr, float *colpart = nullptr) {
     using namespace tgcn;
     TGCN_CHECK(check_common(fn, A, B, C, N, k, n));
-    if (lda < k || ldb < k || ldc < n || lda % 4 != 0 || reinterpret_cast<uintptr_t>(A) % 16 != 0) {
+    if (lda < k || ldb < k || ldc < n || lda % 4 != 0 || !aligned16(A)) {
         set_error("%s: need lda, ldb >= k, ldc >= n, lda %% 4 == 0 and A 16-byte aligned", fn);
         return TGCN_E_INVALID;
     }
@@ -1626,8 +1682,10 @@ int tgcn_set_dropout_row_keys(int64_t split, int64_t key0, int64_t key1) {
     return TGCN_OK;
 }
 
-// p in [0, 1]; p = 1 drops everything (scale 0, as torch does)
-static int make_drop(const char *fn, double p, const uint64_t *seed, int ld, tgcn::Drop &d) {
+// p in [0, 1]; p = 1 drops everything (scale 0, as torch does).  mask / mask_stride: the record the product writes (nn) or
+// reads (nt, tn), checked by the caller.
+static int make_drop(const char *fn, double p, const uint64_t *seed, int ld, tgcn::Drop &d, const uint32_t *mask = nullptr,
+                     int64_t mask_stride = 0) {
     if (!(p >= 0.0 && p <= 1.0) || !seed) {
         tgcn::set_error("%s: need 0 <= p <= 1 and a non-NULL device seed (p=%g)", fn, p);
         return TGCN_E_INVALID;
@@ -1637,14 +1695,17 @@ static int make_drop(const char *fn, double p, const uint64_t *seed, int ld, tgc
     d.key_split = t_key_split;
     d.key0 = t_key0;
     d.key1 = t_key1;
-    if (p >= 1.0) {
-        d.thresh = 0xffffffffu;
-        d.scale = 0.f;
-    } else {
-        d.thresh = static_cast<uint32_t>(std::min(p * 4294967296.0, 4294967295.0));
-        d.scale = static_cast<float>(1.0 / (1.0 - p));
-    }
+    d.thresh = tgcn::drop_threshold(p);           // p = 1: 2^32 - 1
+    d.scale = p >= 1.0 ? 0.f : static_cast<float>(1.0 / (1.0 - p));
+    d.bits = const_cast<uint32_t *>(mask);        // (the nt and tn products only read it)
+    d.bits_stride = mask_stride;
     return TGCN_OK;
+}
+
+// words per row of the record of a [N x width] operand, and: is `mask` such a record?
+static int record_words(int width) { return width > 0 ? 2 * tgcn::drop_bits_wph(width) : 0; }
+static bool is_record(const uint32_t *mask, int64_t mask_stride, size_t words) {
+    return mask && words != 0 && mask_stride >= static_cast<int64_t>(words);
 }
 
 int tgcn_gemm_nn(const float *A, int64_t lda, const float *B, int64_t ldb, float *C, int64_t ldc,
@@ -1668,8 +1729,8 @@ size_t tgcn_dropout_mask_words(int k, int n) {
     // recorded by the fp32 nn product whenever its reduction runs in ONE piece (k <= 256: a launch then sees whole rows of
     // the masked operand; a wide result runs as column groups, each of which writes the same bits) and the split-bf16
     // mode is off (its kernels do not write the record)
-    if (k <= 0 || n <= 0 || k > tgcn::kGroupK || tgcn::g_gemm_split.load(std::memory_order_relaxed) != 0) return 0;
-    return 2 * static_cast<size_t>(tgcn::drop_bits_wph(k));
+    if (n <= 0 || k > tgcn::kGroupK || tgcn::g_gemm_split.load(std::memory_order_relaxed) != 0) return 0;
+    return record_words(k);
 }
 
 int tgcn_gemm_nn_dropout_mask(const float *A, int64_t lda, const float *B, int64_t ldb, float *C, int64_t ldc,
@@ -1677,15 +1738,13 @@ int tgcn_gemm_nn_dropout_mask(const float *A, int64_t lda, const float *B, int64
                               int64_t mask_stride, tgcn_stream stream) {
     const char *fn = "tgcn_gemm_nn_dropout_mask";
     const size_t words = tgcn_dropout_mask_words(k, n);
-    if (!mask || words == 0 || mask_stride < static_cast<int64_t>(words)) {
+    if (!is_record(mask, mask_stride, words)) {
         tgcn::set_error("%s: the mask of a [N x %d] operand takes %zu words per row (0: this product cannot record it); "
                         "mask=%p, stride %lld", fn, k, words, static_cast<void *>(mask), (long long)mask_stride);
         return TGCN_E_INVALID;
     }
     tgcn::Drop d{};
-    TGCN_CHECK(make_drop(fn, p, seed, k, d));
-    d.bits = mask;
-    d.bits_stride = mask_stride;
+    TGCN_CHECK(make_drop(fn, p, seed, k, d, mask, mask_stride));
     return gemm_nn_impl(fn, A, lda, B, ldb, C, ldc, N, k, n, &d, stream);
 }
 
@@ -1702,15 +1761,20 @@ size_t tgcn_gemm_nt_colsum_workspace_bytes(int n) {
     return n > 0 ? sizeof(float) * static_cast<size_t>(tgcn::kTallMaxGrid) * static_cast<size_t>(n) : 0;
 }
 
-int tgcn_gemm_nt_colsum(const float *A, int64_t lda, const float *B, int64_t ldb, float *C, int64_t ldc,
-                        int64_t N, int k, int n, double p, const uint64_t *seed, float *colsum, void *workspace,
-                        size_t workspace_bytes, tgcn_stream stream) {
-    const char *fn = "tgcn_gemm_nt_colsum";
+static int check_colsum_workspace(const char *fn, const float *colsum, int n, const void *workspace, size_t workspace_bytes) {
     if (!colsum || n <= 0 || !workspace || workspace_bytes < tgcn_gemm_nt_colsum_workspace_bytes(n)) {
         tgcn::set_error("%s: colsum and a workspace of %zu bytes are required (%zu given)", fn,
                         tgcn_gemm_nt_colsum_workspace_bytes(n), workspace_bytes);
         return colsum && n > 0 ? TGCN_E_WORKSPACE : TGCN_E_INVALID;
     }
+    return TGCN_OK;
+}
+
+int tgcn_gemm_nt_colsum(const float *A, int64_t lda, const float *B, int64_t ldb, float *C, int64_t ldc,
+                        int64_t N, int k, int n, double p, const uint64_t *seed, float *colsum, void *workspace,
+                        size_t workspace_bytes, tgcn_stream stream) {
+    const char *fn = "tgcn_gemm_nt_colsum";
+    TGCN_CHECK(check_colsum_workspace(fn, colsum, n, workspace, workspace_bytes));
     float *colpart = static_cast<float *>(workspace);
     if (!seed) return gemm_nt_impl(fn, A, lda, B, ldb, C, ldc, N, k, n, nullptr, stream, colsum, colpart);
     tgcn::Drop d{};
@@ -1723,20 +1787,14 @@ int tgcn_gemm_nt_colsum_mask(const float *A, int64_t lda, const float *B, int64_
                              int64_t mask_stride, float *colsum, void *workspace, size_t workspace_bytes,
                              tgcn_stream stream) {
     const char *fn = "tgcn_gemm_nt_colsum_mask";
-    if (!colsum || n <= 0 || !workspace || workspace_bytes < tgcn_gemm_nt_colsum_workspace_bytes(n)) {
-        tgcn::set_error("%s: colsum and a workspace of %zu bytes are required (%zu given)", fn,
-                        tgcn_gemm_nt_colsum_workspace_bytes(n), workspace_bytes);
-        return colsum && n > 0 ? TGCN_E_WORKSPACE : TGCN_E_INVALID;
-    }
-    if (!mask || !seed || mask_stride < 2 * static_cast<int64_t>(tgcn::drop_bits_wph(n))) {
+    TGCN_CHECK(check_colsum_workspace(fn, colsum, n, workspace, workspace_bytes));
+    if (!seed || !is_record(mask, mask_stride, record_words(n))) {
         tgcn::set_error("%s: need the seed and the mask tgcn_gemm_nn_dropout_mask recorded for the [N x %d] operand (rows of "
-                        ">= %d words; stride %lld)", fn, n, 2 * tgcn::drop_bits_wph(n), (long long)mask_stride);
+                        ">= %d words; stride %lld)", fn, n, record_words(n), (long long)mask_stride);
         return TGCN_E_INVALID;
     }
     tgcn::Drop d{};
-    TGCN_CHECK(make_drop(fn, p, seed, n, d));
-    d.bits = const_cast<uint32_t *>(mask);       // read only on this side
-    d.bits_stride = mask_stride;
+    TGCN_CHECK(make_drop(fn, p, seed, n, d, mask, mask_stride));
     return gemm_nt_impl(fn, A, lda, B, ldb, C, ldc, N, k, n, &d, stream, colsum, static_cast<float *>(workspace));
 }
 
@@ -1765,28 +1823,8 @@ static int gemm_tn_impl(const char *fn, const float *A, int64_t lda, const float
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int nb = tn_blocks(N);
-    const int64_t rows_per_wg = ((N + nb - 1) / nb + 1) & ~int64_t(1);  // even: steps are row pairs
-    const int nt = (n + 31) / 32, mt = (k + 31) / 32;
     float *partial = static_cast<float *>(workspace);
-    if (g_gemm_split.load(std::memory_order_relaxed) != 0 && k == 200 && nt == 2 && lda == k && ldg == n && n % 4 == 0 &&
-        reinterpret_cast<uintptr_t>(A) % 16 == 0 && reinterpret_cast<uintptr_t>(G) % 16 == 0) {
-        // split-bf16 products for the weight gradient of the GCN's second layer (16-row K steps through LDS)
-        const int64_t rpw = ((N + nb - 1) / nb + 31) & ~int64_t(31);
-        const size_t lb = sizeof(float) * 2 * (32 * (k + 4) + 32 * (n + 4));
-        if (drop) {
-            TGCN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gemm_tn_split<2, true>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lb)));
-            k_gemm_tn_split<2, true><<<nb, 256, lb, s>>>(A, G, N, k, n, rpw, partial, *drop);
-        } else {
-            TGCN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gemm_tn_split<2, false>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lb)));
-            k_gemm_tn_split<2, false><<<nb, 256, lb, s>>>(A, G, N, k, n, rpw, partial, Drop{});
-        }
-        TGCN_HIP_CHECK(hipGetLastError());
-        k_gemm_tn_reduce<<<(k * n + 63) / 64, 256, 0, s>>>(partial, nb, 32 * mt, 32 * nt, k, n, C, ldc);
-        TGCN_HIP_CHECK(hipGetLastError());
-        return TGCN_OK;
-    }
+    const Drop d = drop ? *drop : Drop{};
     // One launch covers <= 256 columns of A (8 M-tiles, two per wave) x <= 128 columns of G (4 accumulator tiles per
     // M-tile); wider products run as several launches over column chunks of A and / or G, each followed by its
     // reduction -- they share the workspace, in stream order.
@@ -1794,72 +1832,36 @@ static int gemm_tn_impl(const char *fn, const float *A, int64_t lda, const float
         const int kg = std::min(kGroupK, k - i0);
         for (int j0 = 0; j0 < n; j0 += kGroupCols) {
             const int ng = std::min(kGroupCols, n - j0);
-            const int ntg = (ng + 31) / 32, mtg = (kg + 31) / 32;
             const float *Ag = A + i0, *Gg = G + j0;
-            // 16-byte friendly operands with 1, 2 or 4 column tiles of G: the LDS-staged kernel (rows split over the waves)
-            // A width that is not a multiple of 4 (DBpedia's 219 classes: the second group holds 91 columns) is served when
-            // the row reaches to the next multiple of 4 -- a zero-padded buffer (plan.alloc_padded), or columns of a wider
-            // matrix: what is read there lands in result columns nobody stores.  Three tiles run as four.
-            const int ng4 = (ng + 3) & ~3;
-            const int nts = ntg == 3 ? 4 : ntg;
-            const bool staged = (nts == 1 || nts == 2 || nts == 4) && kg % 4 == 0 && lda % 4 == 0 && ldg % 4 == 0 &&
-                                int64_t(j0) + ng4 <= ldg && reinterpret_cast<uintptr_t>(Ag) % 16 == 0 &&
-                                reinterpret_cast<uintptr_t>(Gg) % 16 == 0 && tn_staged_lds_bytes(kg, ng4) <= 160 * 1024 &&
-                                std::getenv("TGCN_TN_STAGED_OFF") == nullptr;
-            if (staged) {
-                const int64_t rpw = ((N + nb - 1) / nb + kTnStageRows - 1) / kTnStageRows * kTnStageRows;
-                const size_t lb = tn_staged_lds_bytes(kg, ng4);
-#define TGCN_TNS2(NT, MT_, DR, BI)                                                                                    \
-    do {                                                                                                              \
-        TGCN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gemm_tn_staged<NT, MT_, DR, BI>),       \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lb)));       \
-        k_gemm_tn_staged<NT, MT_, DR, BI><<<nb, 256, lb, s>>>(Ag, lda, Gg, ldg, N, kg, ng4, rpw, partial,            \
-                                                              drop ? *drop : Drop{}, i0);                           \
-    } while (0)
-                // the recorded mask describes whole rows of A: usable when this launch covers all k columns
-                const bool from_bits = drop && drop->bits && i0 == 0 && kg == k;
-#define TGCN_TNS(NT, MT_, DR)                                                                                         \
-    do {                                                                                                              \
-        if (DR && from_bits) TGCN_TNS2(NT, MT_, DR, DR); else TGCN_TNS2(NT, MT_, DR, false);                         \
-    } while (0)
-#define TGCN_TNS_M(NT, DR)                                                                                            \
-    do {                                                                                                              \
-        if (mtg <= 2) TGCN_TNS(NT, 2, DR); else if (mtg <= 4) TGCN_TNS(NT, 4, DR);                                   \
-        else if (mtg <= 7) TGCN_TNS(NT, 7, DR); else TGCN_TNS(NT, 8, DR);                                           \
-    } while (0)
-                if (drop) {
-                    if (nts == 1) TGCN_TNS_M(1, true); else if (nts == 2) TGCN_TNS_M(2, true); else TGCN_TNS_M(4, true);
-                } else {
-                    if (nts == 1) TGCN_TNS_M(1, false); else if (nts == 2) TGCN_TNS_M(2, false); else TGCN_TNS_M(4, false);
-                }
-#undef TGCN_TNS_M
-#undef TGCN_TNS
-#undef TGCN_TNS2
-                TGCN_HIP_CHECK(hipGetLastError());
-                k_gemm_tn_reduce<<<(kg * ng + 63) / 64, 256, 0, s>>>(partial, nb, 32 * mtg, 32 * nts, kg, ng,
-                                                                     C + int64_t(i0) * ldc + j0, ldc,
-                                                                     drop ? drop->scale : 1.0f);
-                TGCN_HIP_CHECK(hipGetLastError());
-                continue;
+            const TnLeaf l = pick_tn({drop != nullptr, d.bits != nullptr, N, k, i0, kg, j0, ng, lda, ldg, aligned16(Ag),
+                                      aligned16(Gg), g_gemm_split.load(std::memory_order_relaxed) != 0});
+            // the kernels this file builds; `go`: the arguments every family shares
+            auto go = [&](auto *kernel, const auto &...tail) {
+                return launch(kernel, nb, 256, l.lds, s, Ag, lda, Gg, ldg, N, kg, l.cols, l.rpw, partial, d, tail...);
+            };
+            int rc;
+            if (l.family == TnFamily::split) {
+                rc = with_bool(drop != nullptr, [&](auto DR) {
+                    return launch(&k_gemm_tn_split<2, DR()>, nb, 256, l.lds, s, Ag, Gg, N, kg, ng, l.rpw, partial, d);
+                });
+            } else if (l.family == TnFamily::staged) {
+                rc = with_int<1, 2, 4>(l.nt, [&](auto NT) {
+                    return with_int<2, 4, 7, 8>(l.mt, [&](auto MT) {
+                        if (!drop) return go(&k_gemm_tn_staged<NT(), MT(), false, false>, i0);
+                        return l.bits ? go(&k_gemm_tn_staged<NT(), MT(), true, true>, i0)
+                                      : go(&k_gemm_tn_staged<NT(), MT(), true, false>, i0);
+                    });
+                });
+            } else {
+                rc = with_int<1, 2, 3, 4>(l.nt, [&](auto NT) {
+                    return with_bool(drop != nullptr, [&](auto DR) { return go(&k_gemm_tn_partial<NT(), DR()>, i0); });
+                });
             }
-#define TGCN_TN(NT)                                                                                                   \
-    do {                                                                                                              \
-        if (drop)                                                                                                     \
-            k_gemm_tn_partial<NT, true><<<nb, 256, 0, s>>>(Ag, lda, Gg, ldg, N, kg, ng, rows_per_wg, partial, *drop, i0); \
-        else                                                                                                          \
-            k_gemm_tn_partial<NT, false><<<nb, 256, 0, s>>>(Ag, lda, Gg, ldg, N, kg, ng, rows_per_wg, partial, Drop{}, i0); \
-    } while (0)
-            switch (ntg) {
-                case 1: TGCN_TN(1); break;
-                case 2: TGCN_TN(2); break;
-                case 3: TGCN_TN(3); break;
-                default: TGCN_TN(4); break;
-            }
-#undef TGCN_TN
-            TGCN_HIP_CHECK(hipGetLastError());
-            k_gemm_tn_reduce<<<(kg * ng + 63) / 64, 256, 0, s>>>(partial, nb, 32 * mtg, 32 * ntg, kg, ng,
-                                                                 C + int64_t(i0) * ldc + j0, ldc);
-            TGCN_HIP_CHECK(hipGetLastError());
+            TGCN_CHECK(rc);
+            // the staged kernels only keep or zero: the dropout factor is applied here
+            TGCN_CHECK(launch(&k_gemm_tn_reduce, (kg * ng + 63) / 64, 256, 0, s, partial, nb, 32 * ((kg + 31) / 32), 32 * l.nt,
+                              kg, ng, C + int64_t(i0) * ldc + j0, ldc,
+                              l.family == TnFamily::staged && drop ? drop->scale : 1.0f));
         }
     }
     return TGCN_OK;
@@ -1883,15 +1885,13 @@ int tgcn_gemm_tn_dropout_mask(const float *A, int64_t lda, const float *G, int64
                               int64_t N, int k, int n, double p, const uint64_t *seed, const uint32_t *mask,
                               int64_t mask_stride, void *workspace, size_t workspace_bytes, tgcn_stream stream) {
     const char *fn = "tgcn_gemm_tn_dropout_mask";
-    if (!mask || k <= 0 || mask_stride < 2 * static_cast<int64_t>(tgcn::drop_bits_wph(k))) {
+    if (!is_record(mask, mask_stride, record_words(k))) {
         tgcn::set_error("%s: need the mask tgcn_gemm_nn_dropout_mask recorded for this operand (rows of >= %d words; "
-                        "stride %lld)", fn, k > 0 ? 2 * tgcn::drop_bits_wph(k) : 0, (long long)mask_stride);
+                        "stride %lld)", fn, record_words(k), (long long)mask_stride);
         return TGCN_E_INVALID;
     }
     tgcn::Drop d{};
-    TGCN_CHECK(make_drop(fn, p, seed, k, d));
-    d.bits = const_cast<uint32_t *>(mask);       // read only on this side
-    d.bits_stride = mask_stride;
+    TGCN_CHECK(make_drop(fn, p, seed, k, d, mask, mask_stride));
     return gemm_tn_impl(fn, A, lda, G, ldg, C, ldc, N, k, n, workspace, workspace_bytes, &d, stream);
 }
 
