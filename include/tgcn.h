@@ -980,6 +980,56 @@ int tgcn_foldin_levels(int64_t n_docs, const int64_t *rowptr, const int32_t *col
                        const float *dis, int degree_sum, const float *table, int64_t ldt, int n_levels,
                        const tgcn_foldin_level *levels, tgcn_stream stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * tgcn_foldin_routed -- the same for the per-label strategy (perlabel_amazon.py, eval_perlabel.py:57-78): a
+ * top two-layer network on identity features picks the top label k of a document, and the document's class is the arg-max
+ * of label k's own two-layer network on the same graph.  `members` holds K + 1 networks: members[0] is the top network (its
+ * C must equal K), members[1 + k] is routed member k; the K routed members share one h, the top network may have another.
+ * The document's scalars deg_d, dis_d, a_j, a_dd are those of tgcn_foldin_two_layer bit for bit (the same device code).
+ *     z^0   = tgcn_foldin_two_layer on the top network's segments, s1 = NULL, bit for bit         -> top_logits[d, 0:K]
+ *     k     = route_in[d] when route_in is given, else the first arg-max of z^0                   -> route_out[d]
+ *     u^k, z^k = tgcn_foldin_two_layer on member k's segments, s1 = NULL, bit for bit             -> hidden[d, 0:h]
+ *     logits[d, 0:C_k] = z^k,  logits[d, C_k:Cmax] = -inf,  Cmax = max_k C_k  (argmax and softmax of the row are member k's)
+ *     pred[d] = the first arg-max of z^k, or class_map[seg_k + that] when class_map is given, seg_k = sum_{j<k} r4(C_j)
+ * With route_in (int32 [n_docs]) the top network is NOT evaluated: members[0] is not looked at (its h may be 0), top_logits
+ * must be NULL and no column of the top network's segments is read.  A route outside [0, K) -- -1 means "nobody", as in
+ * PerLabelGCN.predict -- gives pred = -1, a logits row of -inf, a hidden row of zeros, and no table row is read for it.
+ * `table` [n_vocab, ldt] is ONE combined table as tgcn_foldin_levels takes it: a word's row holds every network's segments
+ * T1 = W1[w, 0:h] from column t1_col and P = (H1 W2)[w, 0:C] from column p_col, each beginning at a multiple of 4; ONLY the
+ * segments of the networks a document meets are read for it -- never the K h-wide row.  Each network is one
+ * tgcn_foldin_member: t1_col, p_col; W2 [h, C] stride ldw2; b1 [h]; b2 [C]; h, C, act.  class_map int64 [sum_k r4(C_k)] or
+ * NULL is perlabel.column_class_map's output.  Outputs, each of which may be NULL but not all: route_out int32 [n_docs],
+ * top_logits [n_docs, K] stride ldtl, logits [n_docs, Cmax] stride ldl, pred int64 [n_docs], hidden [n_docs, h] stride ldh.
+ * One launch: a wavefront per document, TGCN_FOLDIN_DOCS_PER_WORKGROUP documents per workgroup pass, at most
+ * TGCN_FOLDIN_WORKGROUP_CAP workgroups; a pass over the document's words for the top network, the route through
+ * readfirstlane, a second pass over the same words for member k alone.  W2 and b2 of every network that takes part are
+ * staged in LDS once per workgroup.  No atomics, no workspace, no synchronisation; enqueues on `stream` only (legal under
+ * HIP-graph capture); a document's bits depend on the widths, its own row and its route -- not on the batch.
+ * LDS: tgcn_foldin_routed_lds_bytes(K, h[K + 1], C[K + 1]) = 4 * ( sum_m (r4(h_m C_m) + r4(C_m))
+ *      + TGCN_FOLDIN_DOCS_PER_WORKGROUP * (max_m r4(h_m) + max_m r4(C_m)) ) over the networks that take part (h[0] == 0: no
+ * top network) -- host arithmetic, callable without a GPU; -1 for K outside 1..TGCN_FOLDIN_MAX_MEMBERS, a width outside
+ * 1..256 / 1..128 or routed members of unequal h.  A need above TGCN_FOLDIN_LEVELS_LDS_LIMIT is refused.  TGCN_E_INVALID
+ * before anything is enqueued, with the cause in tgcn_last_error, for that, the size, segment, leading-dimension, alignment
+ * and enum rules of tgcn_foldin_levels applied to every network that takes part, a top network whose C is not K, unequal
+ * member h, no output at all, top_logits together with route_in, and (n_docs > 0) a NULL rowptr, col, val, dis, table, W2,
+ * b1 or b2.  n_docs == 0 launches nothing.  Additive to ABI 7. */
+#define TGCN_FOLDIN_MAX_MEMBERS 64
+typedef struct tgcn_foldin_member {
+    int64_t t1_col;
+    int64_t p_col;
+    const float *W2;
+    int64_t ldw2;
+    const float *b1;
+    const float *b2;
+    int32_t h, C, act, reserved;
+} tgcn_foldin_member;
+int64_t tgcn_foldin_routed_lds_bytes(int n_members, const int32_t *h, const int32_t *C);
+int tgcn_foldin_routed(int64_t n_docs, const int64_t *rowptr, const int32_t *col, const float *val, int64_t n_vocab,
+                       const float *dis, int degree_sum, const float *table, int64_t ldt, int n_members,
+                       const tgcn_foldin_member *members, const int32_t *route_in, const int64_t *class_map,
+                       int32_t *route_out, float *top_logits, int64_t ldtl, float *logits, int64_t ldl, int64_t *pred,
+                       float *hidden, int64_t ldh, tgcn_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,10 @@ two-layer forward is a closed form over tables frozen from the trained model (`t
   * `FoldInLevels(models, graphs)` does the same for the per-level strategy (perlevel_amazon.py, perlevel_dbpedia.py; DESIGN.md
     4.2n): level l >= 2 sees [I | H] with H the link -- softmax or one-hot -- of the level above.  A new document has no
     identity column, so its row of the first layer's operand is H_d W1[N:], a C_{l-1} x h product that the ONE kernel
-    (`tgcn_foldin_levels`) resolves in LDS after ONE pass over the document's words for all levels.
+    (`tgcn_foldin_levels`) resolves in LDS after ONE pass over the document's words for all levels;
+  * `FoldInPerLabel(top_model, net, g, class_map)` does it for the per-label strategy (perlabel_amazon.py, eval_perlabel.py;
+    DESIGN.md 4.2o): the top network's arg-max routes a document to that label's own network, and ONE kernel
+    (`tgcn_foldin_routed`) gathers the top network's rows and then the rows of that ONE member -- never the K h-wide row.
 """
 from __future__ import annotations
 
@@ -138,6 +141,19 @@ def _check_widths(who: str, h: int, C: int, at: str = "") -> None:
                                   f"{lib.tgcn_foldin_max_hidden()} / {lib.tgcn_foldin_max_classes()}")
 
 
+def _check_identity_features(who: str, x) -> None:
+    """`FoldIn` and `FoldInPerLabel` take the sparse identity features of a graph on the GPU and nothing else."""
+    if isinstance(x, hier.HierarchyFeatures):
+        raise NotImplementedError(f"{who}: [I | H] hierarchy features (HierarchyFeatures) are not supported")
+    if not x.is_sparse:
+        raise NotImplementedError(f"{who}: dense features are not supported (sparse identity features only)")
+    if not is_sparse_identity(x):
+        if split_identity_block(x) is not None:
+            raise NotImplementedError(f"{who}: [I | H] hierarchy features are not supported")
+        raise NotImplementedError(f"{who}: non-identity features are not supported (sparse identity features only)")
+    _require_cuda(x, "g.x")
+
+
 def _doc_scalars(rowptr: Tensor, col: Tensor, val: Tensor, dis: Tensor, V: int, degree_sum: str):
     """What both `_composed` methods begin with: a_dd [B, 1] and the plan of the [B, V] matrix of a_j (None for a batch
     without entries).  deg_d comes from `tgcn_gcn_norm` on the bipartite word -> document edges (the plan's own sums, in
@@ -171,8 +187,8 @@ class FoldIn:
         kind = type(model)
         if kind not in (M.GCN, M.EGCN):
             from . import crossval, perlabel, sharded          # (the classes themselves, so that a renamed one cannot slip by)
-            causes = (((crossval.CrossValGCN, crossval.CrossValEGCN, perlabel.PerLabelGCN, perlabel.PerLabelMLP),
-                       "the K-member networks"),
+            causes = (((perlabel.PerLabelGCN,), "the K-member networks: a PerLabelGCN folds in through FoldInPerLabel"),
+                      ((crossval.CrossValGCN, crossval.CrossValEGCN, perlabel.PerLabelMLP), "the K-member networks"),
                       ((sharded.ShardedGCN,), "ShardedGCN: multi-GPU models"),
                       ((M.JumpingKnowledgeNetwork,), "JKN: the jumping-knowledge aggregation has no closed form here"),
                       ((M.MLP,), "MLP has no graph to fold into"))
@@ -181,16 +197,7 @@ class FoldIn:
         convs = list(model.layers)[(1 if kind is M.EGCN else 0):]
         between = model.activation if (kind is M.GCN and getattr(model, "apply_activation", False)) else None
         h, C = _check_two_layer("FoldIn", convs, between, layers_note="; the closed form is the two-layer network's")
-        x = g.x
-        if isinstance(x, hier.HierarchyFeatures):
-            raise NotImplementedError("FoldIn: [I | H] hierarchy features (HierarchyFeatures) are not supported")
-        if not x.is_sparse:
-            raise NotImplementedError("FoldIn: dense features are not supported (sparse identity features only)")
-        if not is_sparse_identity(x):
-            if split_identity_block(x) is not None:
-                raise NotImplementedError("FoldIn: [I | H] hierarchy features are not supported")
-            raise NotImplementedError("FoldIn: non-identity features are not supported (sparse identity features only)")
-        _require_cuda(x, "g.x")
+        _check_identity_features("FoldIn", g.x)
         _check_widths("FoldIn", h, C)
 
     # -- the frozen tables ------------------------------------------------------------------------------------------
@@ -536,6 +543,283 @@ class FoldInLevels:
     def predict_text(self, t2g, docs) -> Tensor:
         """`predict(t2g.transform(docs))` for the fitted `Text2GraphTransformer` that built the graph."""
         return self.predict(t2g.transform(docs))
+
+
+class FoldInPerLabel:
+    """`FoldInPerLabel(top_model, net, g, class_map=None)`: classify documents outside the training graph `g` through the
+    per-label strategy (eval_perlabel.py:57-78).  `top_model` is the two-layer `models.GCN` (linear, or
+    `apply_activation=True` with `nn.ReLU`) trained on the top labels of `g`, whose arg-max picks the member; it may be None
+    when every call passes `route=`.  `net` is the `PerLabelGCN` of the K per-label classifiers on the same `g`, or a sequence
+    of K two-layer linear `GCN` members (eval_perlabel.py:16-19 loads those), which goes through `PerLabelGCN.from_members`.
+    `class_map` is `relabel`'s: K lists, local class -> global class.  The tables are frozen by one eval forward of each
+    network; call `refresh()` after more training (a `net` given as members is rebuilt from them).  Inputs are as on `FoldIn`.
+    Member k's row for document i is what `net.export_members()[k]`'s eval forward gives node N + i of
+    `extended_graph(g, tfidf)`."""
+
+    def __init__(self, top_model, net, g, class_map=None):
+        from . import perlabel
+        self.top_model, self.g = top_model, g
+        self._members = None
+        if isinstance(net, (list, tuple)):
+            self._check_members(net)
+            self._members = list(net)
+            net = perlabel.PerLabelGCN.from_members(self._members)
+        self.net = net
+        self._check(top_model, net, g)
+        self.class_map = None
+        if class_map is not None:
+            counts = [len(m) for m in class_map]
+            if counts != list(net.class_counts):
+                raise ValueError(f"FoldInPerLabel: class_map lists {counts} classes per member, the network has "
+                                 f"{list(net.class_counts)}")
+            self.class_map = perlabel.column_class_map(class_map, g.x.device)
+        self.refresh()
+
+    # -- what is supported ------------------------------------------------------------------------------------------
+    @staticmethod
+    def _check_members(members) -> None:
+        from . import models as M
+        for k, m in enumerate(members):
+            if type(m) is not M.GCN:
+                why = {M.EGCN: "EGCN members: a new document's embedding row is a dense product per document",
+                       M.JumpingKnowledgeNetwork: "JKN members: the jumping-knowledge aggregation has no closed form here",
+                       M.MLP: "MLP members have no graph to fold into"}.get(type(m), "unsupported model type")
+                raise NotImplementedError(f"FoldInPerLabel: member {k} is a {type(m).__name__}, every member must be a two-layer "
+                                          f"models.GCN ({why})")
+            _check_two_layer("FoldInPerLabel", list(m.layers), None, at=f" member {k}:")
+            if getattr(m, "apply_activation", False):
+                raise NotImplementedError(f"FoldInPerLabel: member {k}: other activations than none are not supported between "
+                                          "a member's layers (PerLabelGCN's members are linear)")
+
+    @staticmethod
+    def _check(top_model, net, g) -> None:
+        from . import models as M
+        from . import perlabel, sharded
+        if isinstance(net, perlabel.PerLabelMLP):
+            raise NotImplementedError("FoldInPerLabel: PerLabelMLP needs no fold-in: its members see features only, and "
+                                      "PerLabelMLP.predict on the new rows already is its fold-in")
+        if isinstance(net, sharded.ShardedGCN) or isinstance(top_model, sharded.ShardedGCN):
+            raise NotImplementedError("FoldInPerLabel: ShardedGCN (multi-GPU models) is not supported")
+        if type(net) is not perlabel.PerLabelGCN:
+            raise NotImplementedError(f"FoldInPerLabel takes a PerLabelGCN or a sequence of GCN members, not "
+                                      f"{type(net).__name__}")
+        K, h = net.n_groups, net.n_hidden
+        if K > _lib.FOLDIN_MAX_MEMBERS:
+            raise NotImplementedError(f"FoldInPerLabel: K = {K} members, the kernel takes {_lib.FOLDIN_MAX_MEMBERS}")
+        for k, C in enumerate(net.class_counts):
+            _check_widths("FoldInPerLabel", h, C, at=f" member {k}:")
+        hs, Cs = [0] + [h] * K, [0] + list(net.class_counts)
+        if top_model is not None:
+            if type(top_model) is not M.GCN:
+                why = {M.EGCN: "EGCN", M.JumpingKnowledgeNetwork: "JKN", M.MLP: "MLP has no graph to fold into"}.get(
+                    type(top_model), "unsupported model type")
+                raise NotImplementedError(f"FoldInPerLabel: the top model is a {type(top_model).__name__}, it must be a "
+                                          f"two-layer models.GCN ({why})")
+            between = top_model.activation if getattr(top_model, "apply_activation", False) else None
+            h0, C0 = _check_two_layer("FoldInPerLabel", list(top_model.layers), between, at=" top model:")
+            if C0 != K:
+                raise ValueError(f"FoldInPerLabel: the top model has {C0} classes, the network has K = {K} members")
+            _check_widths("FoldInPerLabel", h0, C0, at=" top model:")
+            hs[0], Cs[0] = h0, C0
+        x = g.x
+        _check_identity_features("FoldInPerLabel", x)
+        for who, m in (("the top model", top_model), ("the network", net)):
+            if m is not None and m.layers[0].in_channels != x.size(1):
+                raise ValueError(f"FoldInPerLabel: {who} takes {m.layers[0].in_channels} features, the graph has {x.size(1)}")
+        need = routed_lds_bytes(hs, Cs)
+        if need > _lib.FOLDIN_LEVELS_LDS_LIMIT:
+            raise NotImplementedError(f"FoldInPerLabel: the W2 of the top model and of all {K} members need {need} bytes of LDS "
+                                      f"next to the waves' slices, a compute unit has {_lib.FOLDIN_LEVELS_LDS_LIMIT}")
+
+    # -- the frozen tables ------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def refresh(self) -> "FoldInPerLabel":
+        """Freeze dis, the combined table, W2 and the biases again from the current parameters: ONE eval forward of the top
+        model and ONE of the K-member network."""
+        from . import perlabel
+        if self._members is not None:
+            self.net = perlabel.PerLabelGCN.from_members(self._members)
+        top, net, g = self.top_model, self.net, self.g
+        V, N, dev = int(g.n_vocab), g.x.size(0), g.x.device
+        first, second = net.layers
+        K, h = net.n_groups, net.n_hidden
+        plan = first.plan(g.x, g.edge_index, g.edge_attr)
+        self.degree_sum, self.n_vocab, self.device = plan.degree_sum, V, dev
+        self.K, self.h, self.C = K, h, list(net.class_counts)
+        self.seg_start = list(net.seg_start)
+        was = net.training
+        net.eval()
+        try:
+            h1 = propagate(plan, first.weight, first.bias)
+            pcat = perlabel.block_diag_xw(h1, second.weight, net.seg_start, net.seg_width).detach()[:V]
+        finally:
+            net.train(was)
+        self.h_top = self.act_top = 0
+        p0 = None
+        if top is not None:
+            t1, t2 = list(top.layers)
+            relu = bool(getattr(top, "apply_activation", False))
+            self.h_top, self.act_top = t1.out_channels, (_lib.ACT_RELU if relu else _lib.ACT_NONE)
+            was = top.training
+            top.eval()
+            try:
+                h0 = propagate(t1.plan(g.x, g.edge_index, g.edge_attr), t1.weight, t1.bias, top.activation if relu else None)
+                p0 = dense.xw(h0, t2.weight).detach()[:V]
+            finally:
+                top.train(was)
+        # one row-padded table: [T1^0 | P^0] and per member [T1^k | P^k]; a document reads two of these pairs
+        h4 = _r4(h)
+        self.t1_col, self.p_col, at = [0], [_r4(self.h_top)], _r4(self.h_top) + (_r4(K) if top is not None else 0)
+        for C in self.C:
+            self.t1_col.append(at)
+            self.p_col.append(at + h4)
+            at += h4 + _r4(C)
+        tab = torch.zeros(V, at, dtype=torch.float32, device=dev)
+        if top is not None:
+            tab[:, :self.h_top] = t1.weight.detach()[:V]
+            tab[:, self.p_col[0]:self.p_col[0] + K] = p0
+            self.W2_top = torch.zeros(self.h_top, _r4(K), dtype=torch.float32, device=dev)
+            self.W2_top[:, :K] = t2.weight.detach()
+            self.b1_top, self.b2_top = _bias_of(t1, self.h_top, dev), _bias_of(t2, K, dev)
+        w1 = first.weight.detach()
+        for k, (s, C) in enumerate(zip(self.seg_start, self.C)):
+            tab[:, self.t1_col[k + 1]:self.t1_col[k + 1] + h] = w1[:V, k * h:(k + 1) * h]
+            tab[:, self.p_col[k + 1]:self.p_col[k + 1] + C] = pcat[:, s:s + C]
+        self._tab = tab
+        self.W2 = second.weight.detach().float().clone()                 # [h, n_cols]: member k's W2 in its segment
+        self.b2 = _bias_of(second, second.weight.size(1), dev)           # [n_cols] likewise
+        self.b1 = torch.zeros(K, h4, dtype=torch.float32, device=dev)    # a 16-byte aligned row per member
+        self.b1[:, :h] = _bias_of(first, K * h, dev).view(K, h)
+        self.dis = gcn_norm_factors(g.edge_index, g.edge_attr, N, 1, self.degree_sum)[0][:V].clone()
+        return self
+
+    _device_csr = FoldIn._device_csr
+
+    def _route(self, route, B: int) -> Optional[Tensor]:
+        if route is None:
+            if self.top_model is None:
+                raise ValueError("FoldInPerLabel: without a top model every call needs `route=`")
+            return None
+        route = torch.as_tensor(route, device=self.device).to(torch.int32).contiguous()
+        if tuple(route.shape) != (B,):
+            raise ValueError(f"FoldInPerLabel: `route` needs one entry per document ({B}), got {tuple(route.shape)}")
+        return route
+
+    # -- compute ----------------------------------------------------------------------------------------------------
+    def _run(self, tfidf, route=None, want_pred=False, want_logits=False, want_top=False, want_hidden=False):
+        """(route int32 [B], top logits, logits, pred int64, hidden): None where not asked for."""
+        rowptr, col, val = self._device_csr(tfidf)
+        B, K, dev = rowptr.numel() - 1, self.K, self.device
+        route = self._route(route, B)
+        if not _FUSED_FOLDIN:
+            return self._composed(rowptr, col, val, route, want_top, want_hidden)
+        c_max = max(self.C)
+
+        def out(width, want):
+            return torch.empty(B, _r4(width), dtype=torch.float32, device=dev) if want else None
+        top_logits, logits, hidden = out(K, want_top), out(c_max, want_logits), out(self.h, want_hidden)
+        pred = torch.empty(B, dtype=torch.int64, device=dev) if want_pred else None
+        route_out = torch.empty(max(B, 1), dtype=torch.int32, device=dev)       # (an output is always asked for)
+        if col.numel() == 0:                       # (data_ptr() of an empty tensor is null)
+            col = torch.zeros(1, dtype=torch.int32, device=dev)
+            val = torch.zeros(1, dtype=torch.float32, device=dev)
+
+        def ptr(t):
+            return t.data_ptr() if (t is not None and B) else None
+        mb = (_lib.FoldinMember * (K + 1))()
+        if self.top_model is not None:
+            mb[0] = _lib.FoldinMember(0, self.p_col[0], self.W2_top.data_ptr(), self.W2_top.stride(0), self.b1_top.data_ptr(),
+                                      self.b2_top.data_ptr(), self.h_top, K, self.act_top, 0)
+        esz = 4
+        for k, (s, C) in enumerate(zip(self.seg_start, self.C)):
+            mb[k + 1] = _lib.FoldinMember(self.t1_col[k + 1], self.p_col[k + 1], self.W2.data_ptr() + esz * s, self.W2.stride(0),
+                                          self.b1[k].data_ptr(), self.b2.data_ptr() + esz * s, self.h, C, _lib.ACT_NONE, 0)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().tgcn_foldin_routed(
+                B, rowptr.data_ptr(), col.data_ptr(), val.data_ptr(), self.n_vocab, self.dis.data_ptr(),
+                _lib.DEGREE_SUMS[self.degree_sum], self._tab.data_ptr(), self._tab.stride(0), K, mb, ptr(route),
+                self.class_map.data_ptr() if self.class_map is not None else None, route_out.data_ptr(),
+                ptr(top_logits), _r4(K), ptr(logits), _r4(c_max), ptr(pred), ptr(hidden), _r4(self.h), _stream_ptr(dev)))
+        return (route_out[:B], None if top_logits is None else top_logits[:, :K], None if logits is None else logits[:, :c_max],
+                pred, None if hidden is None else hidden[:, :self.h])
+
+    def _composed(self, rowptr: Tensor, col: Tensor, val: Tensor, route: Optional[Tensor], want_top: bool, want_hidden: bool):
+        """The same definition from the package's other pieces: the document scalars and ONE plan of the [B, V] matrix of
+        a_j per batch (`_doc_scalars`), ONE SpMM over the whole combined table, `dense.xw` for u^0 W2^0, torch's arg-max, a
+        per-row gather of the member's columns and `dense.xw` per member present in the batch."""
+        B, K, h, dev = rowptr.numel() - 1, self.K, self.h, self.device
+        c_max = max(self.C)
+        a_dd, op = _doc_scalars(rowptr, col, val, self.dis, self.n_vocab, self.degree_sum)
+        if op is not None:
+            sums = op.spmm(self._tab)
+        else:
+            sums = torch.zeros(B, self._tab.size(1), dtype=torch.float32, device=dev)
+        z0 = None
+        if route is None:
+            u0 = sums[:, :self.h_top] + self.b1_top
+            if self.act_top == _lib.ACT_RELU:
+                u0 = torch.relu(u0)
+            z0 = sums[:, self.p_col[0]:self.p_col[0] + K]
+            if B:
+                z0 = (z0 + a_dd * dense.xw(u0.contiguous(), self.W2_top[:, :K])) + self.b2_top
+            route = z0.argmax(dim=1).to(torch.int32) if B else torch.zeros(0, dtype=torch.int32, device=dev)
+        elif want_top:
+            raise ValueError("FoldInPerLabel: with `route=` the top model is not evaluated")
+        logits = torch.full((B, c_max), float("-inf"), dtype=torch.float32, device=dev)
+        hidden = torch.zeros(B, h, dtype=torch.float32, device=dev) if want_hidden else None
+        pred = torch.full((B,), -1, dtype=torch.int64, device=dev)
+        for k in torch.unique(route).tolist():
+            if not 0 <= k < K:
+                continue
+            rows = torch.nonzero(route == k).squeeze(1)
+            s, C = self.seg_start[k], self.C[k]
+            u = sums[rows, self.t1_col[k + 1]:self.t1_col[k + 1] + h] + self.b1[k, :h]
+            z = sums[rows, self.p_col[k + 1]:self.p_col[k + 1] + C]
+            z = (z + a_dd[rows] * dense.xw(u.contiguous(), self.W2[:, s:s + C])) + self.b2[s:s + C]
+            logits[rows, :C] = z
+            local = z.argmax(dim=1)
+            pred[rows] = local if self.class_map is None else self.class_map[s + local]
+            if want_hidden:
+                hidden[rows] = u
+        return route, (z0 if want_top else None), logits, pred, hidden
+
+    @torch.no_grad()
+    def predict(self, tfidf, route=None) -> Tensor:
+        """int64 [B]: the routed member's first arg-max -- the global class when `class_map` was given, else the local one;
+        -1 where `route` names nobody.  `route` (int [B]) replaces the top model's arg-max (eval_perlabel.py:73 routes by a
+        known top label); the top model is then not evaluated."""
+        return self._run(tfidf, route, want_pred=True)[3]
+
+    @torch.no_grad()
+    def predict_levels(self, tfidf) -> Tensor:
+        """int64 [B, 2]: the top label and the class, both from the one launch."""
+        r = self._run(tfidf, None, want_pred=True)
+        return torch.stack([r[0].long(), r[3]], dim=1)
+
+    @torch.no_grad()
+    def logits(self, tfidf, route=None) -> Tuple[Tensor, Tensor]:
+        """(route int64 [B], float32 [B, max C_k]): row i holds the C_k logits of member k = route[i] and -inf behind them,
+        so that arg-max and softmax of the row are the member's own."""
+        r = self._run(tfidf, route, want_logits=True)
+        return r[0].long(), r[2]
+
+    @torch.no_grad()
+    def top_logits(self, tfidf) -> Tensor:
+        """float32 [B, K]: the top model's logits, what `FoldIn(top_model, g).logits(tfidf)` gives."""
+        return self._run(tfidf, None, want_top=True)[1]
+
+    def predict_text(self, t2g, docs) -> Tensor:
+        """`predict(t2g.transform(docs))` for the fitted `Text2GraphTransformer` that built `g`."""
+        return self.predict(t2g.transform(docs))
+
+
+def routed_lds_bytes(h: Sequence[int], C: Sequence[int]) -> int:
+    """`tgcn_foldin_routed_lds_bytes`: the LDS a workgroup of the routed kernel needs for the K + 1 networks of these widths,
+    the top model first (h[0] == 0: none); -1: not a shape it takes.  Host arithmetic."""
+    import ctypes
+    n = len(h)
+    arr = ctypes.c_int32 * max(n, 1)
+    return int(_lib.load().tgcn_foldin_routed_lds_bytes(n - 1, arr(*[int(v) for v in h]), arr(*[int(v) for v in C])))
 
 
 def levels_lds_bytes(h: Sequence[int], C: Sequence[int]) -> int:
