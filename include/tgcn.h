@@ -1030,6 +1030,54 @@ int tgcn_foldin_routed(int64_t n_docs, const int64_t *rowptr, const int32_t *col
                        int32_t *route_out, float *top_logits, int64_t ldtl, float *logits, int64_t ldl, int64_t *pred,
                        float *hidden, int64_t ldh, tgcn_stream stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * tgcn_foldin_layers -- the same for a chain of L = 2, 3 or 4 GCNConv layers: models.py's GCN and EGCN at
+ * n_gcn up to 4, and the layers of its JumpingKnowledgeNetwork, whose row-wise aggregation (JK-LSTM, attention, lin) then
+ * runs on the L output rows.  A new document only receives edges, so no old node's activation changes in ANY layer and d's
+ * row of layer l is a closed form over the frozen word table T^l = (H^{l-1} W_l)[0:n_vocab] (H^0 = x) and d's own previous
+ * row.  The document's scalars deg_d, dis_d, a_j, a_dd are those of tgcn_foldin_two_layer bit for bit (the same device
+ * code), computed once.  With the layer widths w_1 .. w_L:
+ *     x^1 = act_1( (sum_j a_j T^1[w_j, 0:w_1]  +  a_dd s1)            +  b_1 )      s1 NULL = zeros     -> out_1[d, 0:w_1]
+ *     x^l = act_l( (sum_j a_j T^l[w_j, 0:w_l]  +  a_dd (x^{l-1} W_l)) +  b_l )      l = 2 .. L          -> out_l[d, 0:w_l]
+ * with every sum over j in CSR order from zero (one FMA per term), x^{l-1} W_l summed over k = 0 .. w_{l-1}-1 in order (one
+ * FMA per term) and the three terms associated as tgcn_foldin_two_layer associates those of u and z: for l >= 2
+ * fmaf(a_dd, y, sum) + b.  At L = 2 with act_2 = TGCN_ACT_NONE, out_1 / out_2 / pred are tgcn_foldin_two_layer's hidden /
+ * logits / pred bit for bit; the first l outputs of an L-layer call are the l-layer call's on the same segments.
+ * `table` [n_vocab, ldt] is ONE combined table as tgcn_foldin_levels takes it: a word's row holds the segment T^l from column
+ * t_col on, each beginning at a multiple of 4, in any order, gaps allowed; a word's L rows are one contiguous read.  Each
+ * layer is one tgcn_foldin_layer:  W [w_{l-1}, w_l] stride ldw (layer 1: ignored);  b [w_l];  out [n_docs, w_l] stride ldo or
+ * NULL;  t_col, width;  act TGCN_ACT_NONE / TGCN_ACT_RELU;  reserved (ignored).  s1 [w_1] or NULL;  pred int32 [n_docs] or
+ * NULL: the first arg-max of x^L, as tgcn_masked_ce_pred breaks ties.  Nothing beyond column w_l of a segment is read and
+ * nothing outside columns [0, w_l) of an output row is written.  An entry whose column lies outside [0, n_vocab) is skipped
+ * in the sums over j (it still counts in deg_d); rowptr is trusted.
+ * One launch for all layers: a wavefront per document, TGCN_FOLDIN_DOCS_PER_WORKGROUP documents per workgroup pass, at most
+ * TGCN_FOLDIN_WORKGROUP_CAP workgroups; one pass over the document's words gathers all L rows (lane i holds columns
+ * 4i .. 4i+3 of each, 16-byte loads); the layers are then resolved in the wave's LDS slice against W_2 .. W_L and the biases,
+ * which the workgroup stages in LDS once.  No atomics, no workspace, no synchronisation; enqueues on `stream` only (legal under
+ * HIP-graph capture); a document's bits depend on the widths and its own row, not on the batch.
+ * LDS: tgcn_foldin_layers_lds_bytes(L, w[]) = 4 * ( sum_{l>=2} r4(w_{l-1} w_l) + (1 + TGCN_FOLDIN_DOCS_PER_WORKGROUP) *
+ *      sum_l r4(w_l) ), r4 = rounded up to a multiple of 4: W_2 .. W_L, the biases once, and per wave a slice that holds every
+ * layer's row -- host arithmetic, callable without a GPU; -1 for L outside 2..TGCN_FOLDIN_MAX_LAYERS, w_1 outside 1..256 or a
+ * further width outside 1..128 (x W gives a lane two columns).  A need above TGCN_FOLDIN_LEVELS_LDS_LIMIT is refused, the
+ * bytes in the message.  TGCN_E_INVALID before anything is enqueued, with the cause in tgcn_last_error, for that, n_layers
+ * outside 2..4, a width outside its range, ldt outside 4..2^31-1 or not a multiple of 4, a segment that begins off a multiple
+ * of 4 or ends beyond ldt, n_vocab outside 1..2^31-1, n_docs < 0, ldw (l >= 2) or ldo (out given) below the width or not a
+ * multiple of 4, an unknown act / degree_sum, and (n_docs > 0) a NULL rowptr, col, val, dis, table, b or (l >= 2) W, or a
+ * table, s1, W, b or out that is not 16-byte aligned.  n_docs == 0 launches nothing.  Additive to ABI 7. */
+#define TGCN_FOLDIN_MAX_LAYERS 4
+typedef struct tgcn_foldin_layer {
+    const float *W;
+    int64_t ldw;
+    const float *b;
+    float *out;
+    int64_t ldo;
+    int32_t t_col, width, act, reserved;
+} tgcn_foldin_layer;
+int64_t tgcn_foldin_layers_lds_bytes(int n_layers, const int32_t *width);
+int tgcn_foldin_layers(int64_t n_docs, const int64_t *rowptr, const int32_t *col, const float *val, int64_t n_vocab,
+                       const float *dis, int degree_sum, const float *table, int64_t ldt, const float *s1, int n_layers,
+                       const tgcn_foldin_layer *layers, int32_t *pred, tgcn_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

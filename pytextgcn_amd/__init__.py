@@ -14,7 +14,7 @@ from .models import (EGCN, GCN, MLP, JumpingKnowledgeNetwork, enable_fused_dropo
                      enable_fused_hierarchy_embedding, enable_fused_mlp,
                      enable_linear_collapse)
 from .hier import HierarchyFeatures
-from .inductive import FoldIn, FoldInLevels, FoldInPerLabel, enable_fused_foldin, extended_graph
+from .inductive import FoldIn, FoldInDeep, FoldInLevels, FoldInPerLabel, enable_fused_foldin, extended_graph
 from .perlabel import PerLabelGCN, PerLabelMLP
 from .perlevel import AppendedFeatures
 from .reorder import cluster_documents, reorder_documents
@@ -23,4 +23,4 @@ from .text2graph import Text2GraphTransformer
 
 __all__ = ["Text2GraphTransformer", "models", "functional", "optim", "train", "GCN", "EGCN", "JumpingKnowledgeNetwork", "JumpingKnowledge", "jk", "enable_fused_jk", "GCNConv", "Data", "GraphPlan", "plan_for", "colsum",
            "clear_plan_cache", "set_degree_sum", "enable_zero_row_skipping", "enable_activation_reuse", "enable_linear_collapse", "enable_fused_dropout", "enable_fused_embedding", "enable_fused_hierarchy_embedding", "embed", "MLP", "mlp", "enable_fused_mlp", "enable_split_gemms", "reorder_documents", "cluster_documents", "perlabel", "PerLabelGCN", "PerLabelMLP", "hier", "perlevel", "HierarchyFeatures", "AppendedFeatures", "crossval", "CrossValGCN",
-           "MemberAdam", "metrics", "inductive", "FoldIn", "FoldInLevels", "FoldInPerLabel", "extended_graph", "enable_fused_foldin"]
+           "MemberAdam", "metrics", "inductive", "FoldIn", "FoldInDeep", "FoldInLevels", "FoldInPerLabel", "extended_graph", "enable_fused_foldin"]

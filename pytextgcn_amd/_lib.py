@@ -42,6 +42,16 @@ class FoldinMember(ctypes.Structure):
     _fields_ = [("t1_col", c_int64), ("p_col", c_int64), ("W2", c_void_p), ("ldw2", c_int64), ("b1", c_void_p),
                 ("b2", c_void_p), ("h", c_int32), ("C", c_int32), ("act", c_int32), ("reserved", c_int32)]
 
+
+FOLDIN_MAX_LAYERS = 4                                       # TGCN_FOLDIN_MAX_LAYERS
+
+
+class FoldinLayer(ctypes.Structure):
+    """`tgcn_foldin_layer` of include/tgcn.h."""
+    _fields_ = [("W", c_void_p), ("ldw", c_int64), ("b", c_void_p), ("out", c_void_p), ("ldo", c_int64),
+                ("t_col", c_int32), ("width", c_int32), ("act", c_int32), ("reserved", c_int32)]
+
+
 (Q_N_NODES, Q_N_ROWS, Q_NNZ, Q_NNZ_T, Q_SYMMETRIC, Q_ITEMS, Q_ITEMS_T, Q_LONG_ROWS, Q_LONG_ROWS_T,
  Q_SEGMENTS, Q_SEGMENTS_T, Q_DEVICE_BYTES, Q_ROW_BEGIN, Q_HAS_TRANSPOSE, Q_N_ROWS_T, Q_HOT_ROWS,
  Q_HOT_ROWS_T) = range(17)
@@ -227,6 +237,9 @@ SIGNATURES = {
     "tgcn_foldin_routed": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64, c_int,
                                    POINTER(FoldinMember), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
                                    c_void_p, c_void_p, c_int64, c_void_p]),
+    "tgcn_foldin_layers_lds_bytes": (c_int64, [c_int, POINTER(c_int32)]),
+    "tgcn_foldin_layers": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64, c_void_p,
+                                   c_int, POINTER(FoldinLayer), c_void_p, c_void_p]),
     "tgcn_wwedges_create": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p,
                                     POINTER(c_void_p)]),
     "tgcn_wwedges_query": (c_int, [c_void_p, c_int, POINTER(c_int64)]),

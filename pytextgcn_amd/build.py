@@ -16,7 +16,7 @@ _ROOT = os.path.dirname(_PKG)
 CSRC = os.path.join(_PKG, "csrc")
 LIB_DIR = os.path.join(_PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libtgcn.so")
-SOURCES = ["spmm.hip", "colsum.hip", "rows.hip", "train.hip", "perlabel.hip", "crossval.hip", "metrics.hip", "dense.hip", "embed.hip", "hier.hip", "mlp.hip", "mlp_grouped.hip", "blockdiag.hip", "jk.hip", "foldin.hip", "foldin_levels.hip", "foldin_routed.hip", "plan.hip",
+SOURCES = ["spmm.hip", "colsum.hip", "rows.hip", "train.hip", "perlabel.hip", "crossval.hip", "metrics.hip", "dense.hip", "embed.hip", "hier.hip", "mlp.hip", "mlp_grouped.hip", "blockdiag.hip", "jk.hip", "foldin.hip", "foldin_levels.hip", "foldin_routed.hip", "foldin_layers.hip", "plan.hip",
            "graphbuilder.hip", "error.cpp"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "drop_hash.h"), os.path.join(CSRC, "fused_act.h"),
            os.path.join(CSRC, "masked_ce.h"), os.path.join(CSRC, "adam.h"), os.path.join(CSRC, "foldin.h"),

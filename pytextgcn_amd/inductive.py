@@ -19,7 +19,13 @@ two-layer forward is a closed form over tables frozen from the trained model (`t
     (`tgcn_foldin_levels`) resolves in LDS after ONE pass over the document's words for all levels;
   * `FoldInPerLabel(top_model, net, g, class_map)` does it for the per-label strategy (perlabel_amazon.py, eval_perlabel.py;
     DESIGN.md 4.2o): the top network's arg-max routes a document to that label's own network, and ONE kernel
-    (`tgcn_foldin_routed`) gathers the top network's rows and then the rows of that ONE member -- never the K h-wide row.
+    (`tgcn_foldin_routed`) gathers the top network's rows and then the rows of that ONE member -- never the K h-wide row;
+  * `FoldInDeep(model, g)` does it for the deeper models of the reference's surface (textgcn/lib/models.py):
+    `GCN` and `EGCN` with n_gcn up to 4 and the `JumpingKnowledgeNetwork`.  The argument holds at any depth -- no old node's
+    activation changes in any layer -- so d's row of layer l is a closed form over the frozen word table
+    T^l = (H^{l-1} W_l)[:V] and d's own previous row, and ONE kernel (`tgcn_foldin_layers`) carries a document through all L
+    layers in one pass over its words.  The JKN's LSTM aggregation, activation and `lin` are row-wise: they run on d's own L
+    rows.  (The three classes above are two-layer code and keep refusing these models in their own words.)
 """
 from __future__ import annotations
 
@@ -168,6 +174,22 @@ def _doc_scalars(rowptr: Tensor, col: Tensor, val: Tensor, dis: Tensor, V: int, 
     return a_dd, (GraphPlan.from_coo(row, c, a, B, V, with_transpose=False) if c.numel() else None)
 
 
+def _device_csr(tfidf, n_vocab: int, device) -> Tuple[Tensor, Tensor, Tensor]:
+    """What every fold-in class takes as a batch: device tensors (rowptr int64 [B + 1], col int32, val float32), which are
+    trusted, or a scipy sparse matrix [B, n_vocab], which `_host_csr` checks before the copy."""
+    if isinstance(tfidf, (tuple, list)) and len(tfidf) == 3 and all(torch.is_tensor(t) for t in tfidf):
+        rowptr, col, val = tfidf
+        for name, t, dt in (("rowptr", rowptr, torch.int64), ("col", col, torch.int32), ("val", val, torch.float32)):
+            _require_cuda(t, name)
+            if t.dtype != dt or t.dim() != 1 or t.device != device or not t.is_contiguous():
+                raise TypeError(f"FoldIn: `{name}` must be a contiguous 1-D {dt} tensor on {device}")
+        if rowptr.numel() < 1 or col.numel() != val.numel():
+            raise ValueError("FoldIn: rowptr needs n_docs + 1 entries, col and val one per stored entry")
+        return rowptr, col, val
+    rowptr, col, val = _host_csr(tfidf, n_vocab)
+    return tuple(torch.from_numpy(a).to(device) for a in (rowptr, col, val))
+
+
 class FoldIn:
     """`FoldIn(model, g)`: classify documents outside the training graph `g` with the trained `model` -- `models.GCN` (linear,
     or `apply_activation=True` with `nn.ReLU`) or `models.EGCN`, two GCNConv layers, sparse identity features.  The tables
@@ -250,17 +272,7 @@ class FoldIn:
 
     # -- inputs -----------------------------------------------------------------------------------------------------
     def _device_csr(self, tfidf) -> Tuple[Tensor, Tensor, Tensor]:
-        if isinstance(tfidf, (tuple, list)) and len(tfidf) == 3 and all(torch.is_tensor(t) for t in tfidf):
-            rowptr, col, val = tfidf
-            for name, t, dt in (("rowptr", rowptr, torch.int64), ("col", col, torch.int32), ("val", val, torch.float32)):
-                _require_cuda(t, name)
-                if t.dtype != dt or t.dim() != 1 or t.device != self.device or not t.is_contiguous():
-                    raise TypeError(f"FoldIn: `{name}` must be a contiguous 1-D {dt} tensor on {self.device}")
-            if rowptr.numel() < 1 or col.numel() != val.numel():
-                raise ValueError("FoldIn: rowptr needs n_docs + 1 entries, col and val one per stored entry")
-            return rowptr, col, val
-        rowptr, col, val = _host_csr(tfidf, self.n_vocab)
-        return tuple(torch.from_numpy(a).to(self.device) for a in (rowptr, col, val))
+        return _device_csr(tfidf, self.n_vocab, self.device)
 
     # -- compute ----------------------------------------------------------------------------------------------------
     def _run(self, tfidf, want_pred: bool, want_hidden: bool = False):
@@ -811,6 +823,245 @@ class FoldInPerLabel:
     def predict_text(self, t2g, docs) -> Tensor:
         """`predict(t2g.transform(docs))` for the fitted `Text2GraphTransformer` that built `g`."""
         return self.predict(t2g.transform(docs))
+
+
+class FoldInDeep:
+    """`FoldInDeep(model, g)`: classify documents outside the training graph `g` with a trained network of 2 to 4 GCNConv
+    layers -- `models.GCN` (linear, or `apply_activation=True` with `nn.ReLU`), `models.EGCN` or
+    `models.JumpingKnowledgeNetwork`, sparse identity features.  The chain of layers is ONE kernel launch
+    (`tgcn_foldin_layers`); a JKN's aggregation (`jk.lstm_forward`), activation and `lin` then run on the B x L rows it wrote.
+    Everything is frozen from the model's current parameters by one eval forward, layer by layer; call `refresh()` after more
+    training.  Inputs are as on `FoldIn`."""
+
+    def __init__(self, model, g):
+        self.model, self.g = model, g
+        self._check(model, g)
+        self.refresh()
+
+    # -- what is supported ------------------------------------------------------------------------------------------
+    @staticmethod
+    def _convs(model):
+        from . import models as M
+        return list(model.layers)[(1 if type(model) is M.EGCN else 0):]
+
+    @staticmethod
+    def _check(model, g) -> None:
+        from . import models as M
+        kind = type(model)
+        if kind not in (M.GCN, M.EGCN, M.JumpingKnowledgeNetwork):
+            from . import crossval, perlabel, sharded
+            causes = (((perlabel.PerLabelGCN,), "the K-member networks: a PerLabelGCN folds in through FoldInPerLabel"),
+                      ((crossval.CrossValGCN, crossval.CrossValEGCN, perlabel.PerLabelMLP), "the K-member networks"),
+                      ((sharded.ShardedGCN,), "ShardedGCN: multi-GPU models"),
+                      ((M.MLP,), "MLP has no graph to fold into"))
+            why = next((text for classes, text in causes if isinstance(model, classes)), "unsupported model type")
+            raise NotImplementedError(f"FoldInDeep takes models.GCN, models.EGCN and models.JumpingKnowledgeNetwork, not "
+                                      f"{kind.__name__} ({why})")
+        convs = FoldInDeep._convs(model)
+        L = len(convs)
+        if not 2 <= L <= _lib.FOLDIN_MAX_LAYERS:
+            raise NotImplementedError(f"FoldInDeep: n_gcn outside 2..{_lib.FOLDIN_MAX_LAYERS} (the model has {L} GCNConv "
+                                      "layers)")
+        for c in convs:
+            if not (c.add_self_loops and c.normalize) or c.improved:
+                raise NotImplementedError("FoldInDeep: GCNConv(add_self_loops=True, normalize=True, improved=False) only")
+        if kind is M.GCN and getattr(model, "apply_activation", False) and type(model.activation) is not nn.ReLU:
+            raise NotImplementedError("FoldInDeep: other activations than nn.ReLU are not supported between GCN layers "
+                                      f"({type(model.activation).__name__})")
+        _check_identity_features("FoldInDeep", g.x)
+        first_in = model.layers[0].in_features if kind is M.EGCN else convs[0].in_channels
+        if first_in != g.x.size(1):
+            raise ValueError(f"FoldInDeep: the model takes {first_in} features, the graph has {g.x.size(1)}")
+        widths = [c.out_channels for c in convs]
+        lib = _lib.load()
+        h_max, c_max = lib.tgcn_foldin_max_hidden(), lib.tgcn_foldin_max_classes()
+        if widths[0] > h_max or any(w > c_max for w in widths[1:]):
+            raise NotImplementedError(f"FoldInDeep: layer widths {widths} exceed the kernel's {h_max} for the first layer / "
+                                      f"{c_max} for every further one")
+        need = layers_lds_bytes(widths)
+        if need > _lib.FOLDIN_LEVELS_LDS_LIMIT:
+            raise NotImplementedError(f"FoldInDeep: the layers' W_2 .. W_{L} and biases need {need} bytes of LDS next to the "
+                                      f"waves' slices, a compute unit has {_lib.FOLDIN_LEVELS_LDS_LIMIT}")
+
+    # -- the frozen tables ------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def refresh(self) -> "FoldInDeep":
+        """Freeze dis, the combined table [T^1 | .. | T^L], W_2 .. W_L, the biases, s1 and -- for a JKN -- the LSTM,
+        attention and `lin` parameters again from the model's current parameters: ONE eval forward, layer by layer."""
+        from . import models as M
+        model, g = self.model, self.g
+        kind = type(model)
+        convs = self._convs(model)
+        L = len(convs)
+        V, N, dev = int(g.n_vocab), g.x.size(0), g.x.device
+        plan = convs[0].plan(g.x, g.edge_index, g.edge_attr)
+        self.degree_sum, self.n_vocab, self.device = plan.degree_sum, V, dev
+        self.widths = [c.out_channels for c in convs]
+        self.jkn = kind is M.JumpingKnowledgeNetwork
+        relu = kind is M.GCN and bool(getattr(model, "apply_activation", False))
+        self.act = [(_lib.ACT_RELU if (relu and l < L - 1) else _lib.ACT_NONE) for l in range(L)]
+        was_training = model.training
+        model.eval()
+        try:
+            s1 = None
+            if kind is M.EGCN:
+                emb = model.layers[0]
+                if model.takes_fused_path(g.x):
+                    xw = embed.embed_xw(emb.weight, emb.bias, convs[0].weight, 0.0)
+                else:
+                    xw = dense.xw(torch.selu(emb(g.x)), convs[0].weight)
+                s1 = dense.xw(torch.selu(emb.bias.detach()).unsqueeze(0).contiguous(), convs[0].weight).squeeze(0)
+            else:
+                xw = convs[0].weight                     # identity features: x @ W1 is W1; a new row of x is empty
+            segs = [xw.detach()[:V]]
+            for l in range(1, L):
+                h = propagate(plan, xw, convs[l - 1].bias, model.activation if self.act[l - 1] == _lib.ACT_RELU else None)
+                xw = dense.xw(h, convs[l].weight)
+                segs.append(xw.detach()[:V])
+        finally:
+            model.train(was_training)
+        # one row-padded table: a word's L segments are one contiguous read
+        self.t_col, at = [], 0
+        for w in self.widths:
+            self.t_col.append(at)
+            at += _r4(w)
+        tab = torch.zeros(V, at, dtype=torch.float32, device=dev)
+        for l, w in enumerate(self.widths):
+            tab[:, self.t_col[l]:self.t_col[l] + w] = segs[l]
+        self._tab = tab
+        self.W = [None]
+        for l in range(1, L):
+            wl = torch.zeros(self.widths[l - 1], _r4(self.widths[l]), dtype=torch.float32, device=dev)
+            wl[:, :self.widths[l]] = convs[l].weight.detach()
+            self.W.append(wl)
+        self.b = [_bias_of(c, w, dev) for c, w in zip(convs, self.widths)]
+        self.s1 = None if s1 is None else s1.detach().float().clone()
+        self.dis = gcn_norm_factors(g.edge_index, g.edge_attr, N, 1, self.degree_sum)[0][:V].clone()
+        if self.jkn:
+            agg, lin = model.jk, model.lin
+            self._jk_params = [p.detach().clone().contiguous() for p in agg._lstm_parameters()]
+            self._att_w = agg.att.weight.detach().clone().reshape(-1)
+            self._att_b = agg.att.bias.detach().clone()
+            self._lin_wt = lin.weight.detach().clone().t()           # (the layout `lin` itself hands to the product)
+            self._lin_b = None if lin.bias is None else lin.bias.detach().clone()
+            self.n_classes = lin.out_features
+        else:
+            self.n_classes = self.widths[-1]
+        return self
+
+    def _device_csr(self, tfidf) -> Tuple[Tensor, Tensor, Tensor]:
+        return _device_csr(tfidf, self.n_vocab, self.device)
+
+    # -- compute ----------------------------------------------------------------------------------------------------
+    def _chain(self, tfidf, want: Sequence[bool], want_pred: bool):
+        """(the L activations [B, w_l], None where not asked for; pred int32 [B] of x^L or None)."""
+        rowptr, col, val = self._device_csr(tfidf)
+        B, L, dev = rowptr.numel() - 1, len(self.widths), self.device
+        if not _FUSED_FOLDIN:
+            return self._composed(rowptr, col, val, want, want_pred)
+        outs = [torch.empty(B, _r4(w), dtype=torch.float32, device=dev) if on else None for w, on in zip(self.widths, want)]
+        pred = torch.empty(B, dtype=torch.int32, device=dev) if want_pred else None
+        if col.numel() == 0:                       # (data_ptr() of an empty tensor is null)
+            col = torch.zeros(1, dtype=torch.int32, device=dev)
+            val = torch.zeros(1, dtype=torch.float32, device=dev)
+
+        def ptr(t):
+            return t.data_ptr() if (t is not None and B) else None
+        ly = (_lib.FoldinLayer * L)()
+        for l in range(L):
+            ly[l] = _lib.FoldinLayer(self.W[l].data_ptr() if l else None, self.W[l].stride(0) if l else 0, self.b[l].data_ptr(),
+                                     ptr(outs[l]), _r4(self.widths[l]), self.t_col[l], self.widths[l], self.act[l], 0)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().tgcn_foldin_layers(
+                B, rowptr.data_ptr(), col.data_ptr(), val.data_ptr(), self.n_vocab, self.dis.data_ptr(),
+                _lib.DEGREE_SUMS[self.degree_sum], self._tab.data_ptr(), self._tab.stride(0),
+                self.s1.data_ptr() if self.s1 is not None else None, L, ly, ptr(pred), _stream_ptr(dev)))
+        return [None if t is None else t[:, :w] for t, w in zip(outs, self.widths)], pred
+
+    def _composed(self, rowptr: Tensor, col: Tensor, val: Tensor, want: Sequence[bool], want_pred: bool):
+        """The same definition from the package's other pieces: the document scalars and ONE plan of the [B, V] matrix of
+        a_j per batch (`_doc_scalars`), one SpMM per layer on that layer's segment, `dense.xw` for x^{l-1} W_l and torch for
+        the bias and the activation."""
+        B, dev = rowptr.numel() - 1, self.device
+        a_dd, op = _doc_scalars(rowptr, col, val, self.dis, self.n_vocab, self.degree_sum)
+        acts, x = [], None
+        for l, w in enumerate(self.widths):
+            if op is not None:
+                s = op.spmm(self._tab[:, self.t_col[l]:self.t_col[l] + w])
+            else:
+                s = torch.zeros(B, w, dtype=torch.float32, device=dev)
+            if l == 0:
+                if self.s1 is not None:
+                    s = s + a_dd * self.s1
+            elif B:
+                s = s + a_dd * dense.xw(x.contiguous(), self.W[l][:, :w])
+            x = s + self.b[l]
+            if self.act[l] == _lib.ACT_RELU:
+                x = torch.relu(x)
+            acts.append(x)
+        pred = x.argmax(dim=1).to(torch.int32) if want_pred else None
+        return [a if on else None for a, on in zip(acts, want)], pred
+
+    def _aggregate(self, acts: List[Tensor]):
+        """A JKN's rows after the chain: (logits [B, C], alpha [B, L]) -- `jk.lstm_forward` (the fused kernel where the model's
+        own forward takes it, the ReLU in its epilogue), any other activation module, then `lin` on the package's kernels."""
+        from . import jk
+        from .conv import features_times
+        model = self.model
+        relu = type(model.activation) is nn.ReLU
+        x, alpha = jk.lstm_forward(acts, self._jk_params, self._att_w, self._att_b, relu, model.jk.takes_fused_path(),
+                                   model.jk.chunk_rows)
+        if not relu:
+            x = model.activation(x)
+        if x.size(0) == 0:
+            return torch.zeros(0, self.n_classes, dtype=torch.float32, device=self.device), alpha
+        z = features_times(x, self._lin_wt, self._lin_wt.size(0))
+        return (z if self._lin_b is None else z + self._lin_b), alpha
+
+    def _run(self, tfidf, want_pred: bool):
+        """(logits, pred int64 or None)."""
+        L = len(self.widths)
+        if self.jkn:
+            z = self._aggregate(self._chain(tfidf, [True] * L, False)[0])[0]
+            return z, (z.argmax(dim=1) if want_pred else None)
+        acts, pred = self._chain(tfidf, [False] * (L - 1) + [True], want_pred)
+        return acts[-1], (pred.long() if want_pred else None)
+
+    @torch.no_grad()
+    def logits(self, tfidf) -> Tensor:
+        """float32 [B, C]: row i holds what the model's eval forward gives node N + i of `extended_graph(g, tfidf)`."""
+        return self._run(tfidf, False)[0]
+
+    @torch.no_grad()
+    def predict(self, tfidf) -> Tensor:
+        """int64 [B]: the first arg-max of every row of `logits(tfidf)` (GCN / EGCN: taken inside the same launch)."""
+        return self._run(tfidf, True)[1]
+
+    @torch.no_grad()
+    def activations(self, tfidf) -> List[Tensor]:
+        """L tensors float32 [B, w_l]: row i of the l-th holds layer l's eval-mode output for node N + i of
+        `extended_graph(g, tfidf)` -- what a JKN's aggregation sees."""
+        return self._chain(tfidf, [True] * len(self.widths), False)[0]
+
+    @torch.no_grad()
+    def alpha(self, tfidf) -> Tensor:
+        """float32 [B, L]: a JKN's attention weights over the layers for every new document."""
+        if not self.jkn:
+            raise TypeError("FoldInDeep.alpha: the model is not a JumpingKnowledgeNetwork")
+        return self._aggregate(self._chain(tfidf, [True] * len(self.widths), False)[0])[1]
+
+    def predict_text(self, t2g, docs) -> Tensor:
+        """`predict(t2g.transform(docs))` for the fitted `Text2GraphTransformer` that built `g`."""
+        return self.predict(t2g.transform(docs))
+
+
+def layers_lds_bytes(widths: Sequence[int]) -> int:
+    """`tgcn_foldin_layers_lds_bytes`: the LDS a workgroup of the layer-chain kernel needs for these widths (-1: not a shape it
+    takes).  Host arithmetic."""
+    import ctypes
+    n = len(widths)
+    arr = ctypes.c_int32 * max(n, 1)
+    return int(_lib.load().tgcn_foldin_layers_lds_bytes(n, arr(*[int(v) for v in widths])))
 
 
 def routed_lds_bytes(h: Sequence[int], C: Sequence[int]) -> int:
